@@ -19,7 +19,9 @@ LOCAL_RANK, WORLD_SIZE, MASTER_* from the environment).  Started plainly with --
 this process starts the N ranks itself as child processes, before anything here touches a
 GPU; with fewer than N GPUs visible it exits non-zero instead of reporting a smaller run.
 
-Prints one JSON line on rank 0 (see the driver contract).
+Prints one JSON line on rank 0 (see the driver contract).  `--dump-outputs DIR` also writes what the last timed step
+computed (the headline's grids, float64 .npy files; see dump_outputs), from a timed region that starts from the same
+state in every run with the same arguments.
 """
 from __future__ import annotations
 
@@ -51,6 +53,10 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 # (78.6 TFLOP/s = 1024 SIMDs x 16 lanes x 2 flop x 2.4 GHz), MI355X_MICROARCH.md
 N_SIMD, CLOCK_GHZ, FP64_CYCLES_PER_WAVE_INSTR = 1024, 2.4, 4
 VALU_PEAK_GWINST = N_SIMD * CLOCK_GHZ / FP64_CYCLES_PER_WAVE_INSTR  # 614.4 G wavefront instructions per second
+# --dump-outputs: a grid of more cells is written as a fixed seeded sample of this many cells plus its ring means
+# (8 MB of float64 per grid: the six grids of the ideal EOS stay below 64 MB)
+DUMP_MAX_CELLS = 1 << 20
+DUMP_SEED = 1234
 
 # SURVEY.md section 8(d) / BASELINE.md section 3, the contract figure of the WHOLE step: 4-pass model
 # A source+viscosity 5|7, B radial transport 8|10, C azimuthal transport 11|13, D velocities+floors+CFL 8|10
@@ -112,6 +118,10 @@ def parse_args():
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1,
                     help="with --dry-run-ranks: this rank exits with code 3 before the rendezvous (tests the parent's "
                          "handling of a dying rank)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline left in the grids a caller downloads as "
+                         "DIR/<name>.npy (float64; see dump_outputs).  The headline context is then rewound to its "
+                         "initial state after the settle steps, so the timed steps start from the same state in every run")
     return ap.parse_args()
 
 
@@ -199,6 +209,7 @@ class Leg:
         self.radii = lib.radii(d)
         self.fields = lib.initial_fields(d.copy(), self.radii)  # slab-local
         self.ctx = driver.make_context(lib, d, fields=self.fields, radii=self.radii, bodies=bodies)
+        self.clock0 = self.ctx.clock  # before any step: where rewind() sets the clock back to
         self.ctx.set_stream(torch.cuda.current_stream().cuda_stream)
         self.adi = 1 if d.eos == B.EOS_IDEAL else 0
         self.multi = env["world"] > 1 and d.nranks > 1
@@ -280,6 +291,26 @@ class Leg:
         else:
             for _ in range(2):
                 ctx.calculate_timestep(ctx.cfl())
+
+    def rewind(self):
+        """Back to the state the context was created with -- the ABI's restart path: the state grids uploaded again,
+        the clock set back, init_physics -- and sim::init's pre-loop calls again: however many steps ran before, the
+        next step starts from the same state."""
+        B, ctx = self.B, self.ctx
+        for f, a in zip((B.F_SIGMA, B.F_VRAD, B.F_VAZI, B.F_ENERGY), self.fields):
+            ctx.upload(f, a)
+        ctx.clock = self.clock0
+        ctx.init_physics()
+        self.pre_loop()
+
+    def outputs(self):
+        """What a caller of the step loop downloads after it: the state grids, and Q+ / Q- of the last step with the
+        energy equation (fcpt_run_steps writes them in the last step of a call)."""
+        out = self.ctx.state()
+        if self.adi:
+            out["qplus"] = self.ctx.download(self.B.F_QPLUS)
+            out["qminus"] = self.ctx.download(self.B.F_QMINUS)
+        return out
 
     def sync(self):
         self.ctx.synchronize()
@@ -448,6 +479,12 @@ def main():
     ctx.profile_start([names.index(dominant)], max_launches=args.steps + 8)
     ctx.profile_stop()
     settle_steps = leg.settle() + cal
+    if args.dump_outputs:
+        # the settle loop stops on GPU time, so how many steps it takes varies from run to run: back to the initial
+        # state, and a fixed number of steps to bring the clocks up again -- the timed steps start from the same state
+        leg.rewind()
+        leg.run(SETTLE_STEPS)
+        settle_steps = SETTLE_STEPS
     leg.run(args.warmup)
 
     # ---- timed region ---------------------------------------------------------
@@ -460,6 +497,9 @@ def main():
     dom = ctx.profile_stop()[dominant]
     ctx.set_option("profile_stride", 1)
     per_rank_ms = [1e3 * t / args.steps for t in per_rank_s]
+    dumped = None
+    if args.dump_outputs:   # before the blocks below step on
+        dumped = dump_outputs(args.dump_outputs, leg.outputs(), ctx.clock, prefix=f"rank{rank}_" if multi else "")
 
     # the same block again, a few times: a timed region of K x 0.4 ms can end before the GPU clocks have settled
     blocks = []
@@ -533,6 +573,10 @@ def main():
             # rocprofv3 names (fcpt_kernel_name): comparable with profiles/*_kernel_stats.csv line by line
             "kernel_ms_per_step": {k: v[0] / cal for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])[:8]},
         }
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dumped,
+                                   "note": "the headline context was rewound to its initial state after the settle steps "
+                                           "and ran untimed_steps_before_timed_region steps from there"}
         if strong_row is not None:
             out["strong_scaling"] = strong_row
         if world == 1 and not rehearse and not args.no_configs:
@@ -545,6 +589,31 @@ def main():
     if multi:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, grids, clock, prefix=""):
+    """--dump-outputs: every grid as float64 `<prefix><name>.npy`, whole when it has at most DUMP_MAX_CELLS cells;
+    otherwise `<name>_sample.npy`, the values at DUMP_MAX_CELLS flat indices drawn once per grid shape with seed
+    DUMP_SEED (sorted, without repetition), and `<name>_ring_mean.npy`, the mean over phi of every ring of the whole
+    grid.  `clock.npy` holds time, last dt and the step counter.  Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    written, picks = [], {}
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        written.append(prefix + name + ".npy")
+
+    for name, a in grids.items():
+        if a.size <= DUMP_MAX_CELLS:
+            save(name, a)
+            continue
+        if a.shape not in picks:
+            picks[a.shape] = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_CELLS, replace=False))
+        save(name + "_sample", a.reshape(-1)[picks[a.shape]])
+        save(name + "_ring_mean", a.mean(axis=1))
+    save("clock", [clock.time, clock.last_dt, float(clock.n_hydro_iter)])
+    return written
 
 
 def roofline(dominant, dom_ms, launches, stride, adi, slab_cells, pmc, value, world):

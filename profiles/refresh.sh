@@ -1,7 +1,7 @@
 #!/bin/bash
 # Regenerates the judged profile artefacts on the GPU box into gpurun_out/refresh (copy them to profiles/ afterwards):
 # rocprofv3 kernel stats of the bench command (isothermal + ideal EOS), the PMC passes, the bench JSON lines.
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 O=$R/gpurun_out/refresh
 rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # Collects PMC counters for the bench workload in separate rocprofv3 passes
 # (kernel-trace only; no sys/hip/hsa tracing together with --pmc).
 # usage: profiles/run_pmc.sh <outdir> [bench args]
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$1; shift
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # rocprofv3 average duration of selected kernels for the in-tree build and an alt build (FCPT_LIB_PATH): two bench runs each
 # usage: profiles/tools/kernel_avg.sh <alt name> "<kernel name fragment> ..." [bench args]   (run on the GPU box)
 ALT=$1; KS=$2; shift; shift
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for v in base $ALT base $ALT; do
   if [ $v = base ]; then unset FCPT_LIB_PATH; else export FCPT_LIB_PATH=$R/fargocpt_amd/libfargocpt_hip_$v.so; fi

@@ -2,7 +2,7 @@
 # Issue/stall counters of the dominant kernels for several builds of the library (see ab_multi.sh), separate
 # rocprofv3 --pmc passes (kernel trace only).
 # usage: profiles/tools/pmc_ab.sh "<name> ..." <outdir> [kernel substring] [extra bench args]   (run on the GPU box)
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 NAMES=$1; OUT=$2; KSUB=${3:-k_transport_fused}; shift; shift; shift
 case $OUT in /*) ;; *) OUT=$R/$OUT;; esac
 mkdir -p $OUT
