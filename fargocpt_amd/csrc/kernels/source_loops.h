@@ -648,6 +648,10 @@ __device__ __forceinline__ void substep3_cell(const Dev &P, int i, int j, double
     if (i < 1 || i >= P.nr - 1) { // SubStep3 itself runs on rings [1, Nr-1)
         if (update_energy == 2)
             P.energy[IDX(i, j)] = clamp_energy(P, P.energy[IDX(i, j)], P.sigma[IDX(i, j)]);
+        // calculate_qplus / calculate_qminus clear both grids on every ring before they fill [1, Nr-1)
+        // (SourceEuler.cpp:614-630,931-950): the edge rings hold 0, not what an earlier launch left there
+        P.qplus[IDX(i, j)] = 0.0;
+        P.qminus[IDX(i, j)] = 0.0;
         return;
     }
     const double dt = P.clk->dt;

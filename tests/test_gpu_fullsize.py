@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 
 from fargocpt_amd import binding as B, driver, setups
-from tests.util import perturb, rel_err, run_pair
+from tests.util import check_cells, perturb, rel_err, run_pair
 
 pytestmark = pytest.mark.gpu
 NR, NPHI = 2048, 4096
@@ -33,6 +33,7 @@ def _check_pair(res, fields):
     errs = {k: rel_err(sa[k], sb[k]) for k in fields}
     assert all(np.isfinite(sa[k]).all() for k in fields)
     assert max(errs.values()) <= TOL, errs
+    check_cells(res, fields, TOL)
     return errs
 
 

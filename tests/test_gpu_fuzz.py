@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from fargocpt_amd import binding as B, setups
-from tests.util import rel_err, run_pair
+from tests.util import GROWTH_CAP, _tolerance, rel_err, run_pair
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -102,22 +102,8 @@ def draw(lib, seed):
     return d, nslabs, planet
 
 
-GROWTH_CAP = 1.0e4   # widened bar at most 1e-13 x 1e4 = 1e-9; a more violent draw is compared over fewer steps instead
 RELAXED = []         # (test, seed, steps, growth, tolerance): every draw that did not meet the plain 1e-10 bar
 COMPARED = []        # every draw that was compared at all
-
-
-def _tolerance(oracle_run, b, fields, worst):
-    """1e-10, unless the draw is an unstable flow that amplifies rounding by orders of magnitude per step: then
-    what the oracle does to cell-wise 1e-15 relative noise on its own input over the same steps (measured only
-    when the plain bar is missed), never more than GROWTH_CAP."""
-    if worst <= TOL:
-        return TOL, 1.0
-    noise = 1.0e-15
-    b2 = oracle_run(noise)
-    growth = max(rel_err(b2[k], b[k]) for k in fields) / noise
-    # the two paths differ by a few 1e-14 before any amplification; one noise realisation
-    return max(TOL, 1.0e-13 * min(growth, GROWTH_CAP)), growth
 
 
 def _judge(test, seed, attempt):
