@@ -63,12 +63,11 @@ void options_from_environment(Options &o)
     o.source_graded = -1;
     o.transport_big = o.transport_ladder = o.transport_rank_grade = -1;
     o.transport_fallback = o.transport_split = o.fused_source = o.march_source = o.march_source_adi = 1;
-    o.theta_march = o.theta_fused = o.cfl_rings = o.cfl_split = o.source_ring_parts = o.fused_damping = 1;
+    o.theta_march = o.cfl_rings = o.cfl_split = o.source_ring_parts = o.fused_damping = 1;
     o.cfl_wide_blocks = -1;
     o.gate_in_boundary = 1;
     o.cfl_fold_in_source = -1;
     o.inline_potential = 1;
-    o.cfl_thermal = 0; // measured: the kernel that stores the terms spills (28 B) and loses more than the CFL pass gains
     o.bc_fold = 1;
     o.bc_in_cfl = 1;
     o.comm_overlap = 0;
@@ -166,10 +165,6 @@ void apply_options(fcpt_ctx *c, bool at_create = true)
         c->P.adiabatic && c->fused_source && c->march_source && c->P.nphi >= 128 && o.march_source_adi != 0;
     c->P.lazy_derived = adi_march ? 1 : 0;
     c->P.inline_potential = (adi_march && !c->P.leapfrog && o.inline_potential != 0 && !c->P.accel_force) ? 1 : 0;
-    // the transport leaves the cell-local CFL terms only where the CFL kernel that reads them will run (lazy derived
-    // quantities, Euler: the leapfrog's second kick changes e after the transport)
-    c->P.cfl_thermal = (adi_march && !c->P.leapfrog && o.cfl_thermal != 0) ? c->thermal_grid : nullptr;
-    c->thermal_valid = false;
     c->P.damp_in_step = (c->damp_foldable && o.fused_damping != 0) ? 1 : 0;
     c->cfl_interior = false;
     c->potential_valid = false;
@@ -508,7 +503,6 @@ int fcpt_create(const fcpt_desc *d, const double *radii, fcpt_ctx **out)
     AL(rmpB, ns) AL(rmmB, ns) AL(lpB, ns) AL(lmB, ns) AL(sigB, ns) AL(eB, ns)
     AL(vmean, (size_t)nr + 1) AL(vconst, (size_t)nr) AL(nshift, (size_t)nr) AL(clk, 1) AL(shift_jump, 8)
     AL(cfl_part, (size_t)(nr + 256) * (size_t)((nphi + 255) / 256 + 1))
-    AL(cfl_tickets, 32)
     P.ring_pstride = nphi / 32 + 4;
     AL(ring_part, (size_t)nr * P.ring_pstride)
     P.stabilize = d->stabilize_viscosity;
@@ -522,10 +516,6 @@ int fcpt_create(const fcpt_desc *d, const double *radii, fcpt_ctx **out)
     if (P.accel_force) {
         AL(accel_r, nv) AL(accel_az, nv) // zero-filled: rows 0 and nr are never written (Pframeforce.cpp:121-123)
     }
-    double *thermal_grid = nullptr; // ideal EOS: the cell-local CFL terms left by the marching transport
-    if (!rc && d->eos == FCPT_EOS_IDEAL)
-        rc = dev_alloc(c, &thermal_grid, ns);
-    c->thermal_grid = thermal_grid;
     if (!rc && d->eos == FCPT_EOS_IDEAL)
         rc = dev_alloc(c, &P.qdiff, ns);
 #undef AL
@@ -779,8 +769,8 @@ int fcpt_get_option(const fcpt_ctx *c, const char *name, int32_t *value)
         *value = (stamps[2] != 0 && stamps[0] == stamps[2]) ? 1 : 0;
         return FCPT_OK;
     }
-    if (!std::strcmp(name, "coop_active")) { // 1: fcpt_run_steps takes the one-kernel-per-step path on this grid
-        *value = c->coop_active ? 1 : 0;
+    if (!std::strcmp(name, "coop_active")) { // always 0: fcpt_run_steps has no one-kernel-per-step path
+        *value = 0;
         return FCPT_OK;
     }
     if (!std::strcmp(name, "graph_cycle")) {
@@ -974,14 +964,11 @@ int fcpt_upload(fcpt_ctx *c, int32_t f, const double *host)
         c->pressure_valid = false;
         c->potential_valid = false;
         c->stepped = false;
-        c->thermal_valid = false;
         c->ghosts_unknown = true;
         drop_graph(c); // its launches were chosen for ghost rings that satisfied the boundary conditions
     }
-    if (f == FCPT_F_QPLUS || f == FCPT_F_QMINUS) {
-        c->thermal_valid = false;
+    if (f == FCPT_F_QPLUS || f == FCPT_F_QMINUS)
         c->qdiff_valid = false;
-    }
     if (f == FCPT_F_SCALE_HEIGHT)
         c->potential_valid = false;
     c->cfl_interior = false;
@@ -1139,7 +1126,6 @@ int fcpt_init_physics(fcpt_ctx *c)
         return rc;
     c->potential_valid = false;
     c->pressure_valid = true;
-    c->thermal_valid = false;
     HIPCHK(hipGetLastError());
     return FCPT_OK;
 }
@@ -1155,7 +1141,6 @@ int fcpt_recalculate_derived(fcpt_ctx *c)
     c->stepped = false;
     c->cfl_interior = false;
     c->potential_valid = false;
-    c->thermal_valid = false;
     if (c->P.adiabatic && !c->P.lazy_derived) {
         launch_derived(c->P, c->stream);
         c->pressure_valid = true;

@@ -68,8 +68,6 @@ struct fcpt_ctx {
     bool fold_pending = false;
     bool cfl_interior = false; // fcpt_cfl_begin evaluated the interior rings of the current state
     bool damp_any = false;     // this slab holds rings of a damping zone
-    double *thermal_grid = nullptr; // storage of Dev::cfl_thermal (the view's pointer is null when the option is off)
-    bool thermal_valid = false;     // ... and it describes the current state (set by a marching-transport step)
     bool qdiff_valid = false;       // Dev::qdiff holds Q+ - Q- of the grids (written by the last kick's march)
     std::vector<int> ring_ref_damped; // per ring: 1 if the folded damping loads reference values there (costlier rings of the transport)
     int *sm_sched_dev = nullptr;      // storage of Dev::sm_sched
@@ -105,7 +103,6 @@ struct fcpt_ctx {
     hipGraph_t graph = nullptr;
     hipStream_t capture_stream = nullptr;
     int graph_cycle = 0;
-    bool coop_active = false; // the last fcpt_run_steps ran its steps as one cooperative kernel each
     long long graph_replays = 0; // hipGraphLaunch calls issued so far (read-only option "graph_replays")
     bool graph_failed = false;
     Dev graph_P;

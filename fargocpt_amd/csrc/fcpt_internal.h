@@ -137,7 +137,7 @@ struct alignas(64) DampRow { // ring i (nr + 1 rows: v_r has row nr)
 // variables of the same names only seed the defaults in fcpt_create; nothing on the launch path reads the
 // environment.  A value of -1 means "not set: the launcher's built-in choice".
 struct Options {
-    int transport_fused;    // 0: off, 1 | 2: k_transport_fused with 1 | 2 cells per lane (rings of >= 256 cells)
+    int transport_fused;    // 0: off; any other value: the built-in choice (k_transport_fused on rings of >= 256 cells)
     int transport_rows;     // rings per marching chunk of k_transport_fused (> 0: equal chunks of that many rings)
     int transport_graded;   // 1: chunks of graded length, long ones first (transport_schedule()); 0: equal chunks
     int transport_big;      // graded: rings per chunk of the first round (-1: from the grid and the wavefront slots)
@@ -152,16 +152,14 @@ struct Options {
     int march_source;       // 0: the three fused source kernels instead of the marching one
     int march_source_adi;   // 0: ... for the ideal EOS only
     int theta_march;        // 0: per-pass azimuthal kernels
-    int theta_fused;        // 0: same (older name, kept)
     int cfl_rings;          // 0: k_ring_mean + k_cfl_cells instead of k_cfl_rings
-    int cfl_wide_blocks;    // rings of 2049 .. 4096 cells: 0: k_cfl_rings with 256 threads per ring, 1 | 2: 1024 | 512 threads and all loads ahead of the ring sum, -1: built-in (isothermal 2, ideal EOS 0)
+    int cfl_wide_blocks;    // rings of 2049 .. 4096 cells: 0: k_cfl_rings with 256 threads per ring, any other value: 512 threads and all loads ahead of the ring sum, -1: built-in (isothermal 512, ideal EOS 256)
     int cfl_fold_in_source; // fcpt_run_steps on one slab: 0: k_cfl_final as its own launch, 1: every workgroup of the marching source kernel folds the partial maxima itself (-1: built-in)
     int gate_in_boundary;   // fcpt_run_steps on one slab: 1: the idle gated launch of the fallback transport and the final boundary call of the step are ONE launch where the boundary call is its own kernel (grids below 4 M cells)
     int cfl_split;          // fcpt_cfl_begin evaluates the interior rings ahead of the ghost exchange
     int source_ring_parts;  // 0: the transport's ring mean re-reads v_phi
     int fused_damping;      // 0: the wave damping as separate kernels in the final boundary call
     int inline_potential;   // 0: ideal EOS: k_potential every step instead of the evaluation inside k_source_march_adi
-    int cfl_thermal;        // 1: ideal EOS: the transport stores the cell-local CFL terms, the CFL kernel reads 3 grids, not 6
     int bc_fold;            // 0: the pre-transport boundary call as its own launch instead of inside the source march
     int bc_in_cfl;          // 0: fcpt_run_steps launches the final boundary call of a step by itself instead of inside the next CFL launch (1: on grids of >= 4M cells, 2: on any grid)
     int comm_overlap;       // fcpt_exchange: transfers on the library's communication stream under the interior CFL
@@ -171,8 +169,8 @@ struct Options {
 };
 #define FCPT_OPTION_NAMES                                                                                        \
     X(transport_fused) X(transport_rows) X(transport_graded) X(transport_big) X(transport_ladder) X(transport_rank_grade) X(source_rows) X(source_graded) X(theta_rows) X(transport_fallback) X(transport_split)    \
-    X(fused_source) X(march_source) X(march_source_adi) X(theta_march) X(theta_fused) X(cfl_rings) X(cfl_wide_blocks) X(cfl_fold_in_source) X(gate_in_boundary) X(cfl_split)   \
-    X(source_ring_parts) X(fused_damping) X(inline_potential) X(cfl_thermal) X(bc_fold) X(bc_in_cfl) X(comm_overlap) X(comm_loopback) X(graph_steps) X(profile_stride)
+    X(fused_source) X(march_source) X(march_source_adi) X(theta_march) X(cfl_rings) X(cfl_wide_blocks) X(cfl_fold_in_source) X(gate_in_boundary) X(cfl_split)   \
+    X(source_ring_parts) X(fused_damping) X(inline_potential) X(bc_fold) X(bc_in_cfl) X(comm_overlap) X(comm_loopback) X(graph_steps) X(profile_stride)
 
 // Everything a kernel needs: geometry, grids, parameters.  Passed by value.
 struct Dev {
@@ -237,12 +235,9 @@ struct Dev {
     int damp_in_step;
     CArrI nshift_c;
     double *cfl_part; // per-block maxima of the CFL reduction
-    double *cfl_thermal; // ideal EOS: invdt1^2 + invdt5^2 + invdt6^2 per cell, left by the marching transport (null: off)
-    int cfl_thermal_on;  // ... and valid for the current state: k_cfl_rings reads it instead of Sigma, e, Q+, Q-
     double *qdiff;       // ideal EOS: Q+ - Q- of the last kick, written by k_source_march_adi beside Q+ and Q-
     int qdiff_on;        // ... and current: the CFL kernel reads it instead of the two grids
     double *cfl_export;  // non-null: the final fold also leaves the slab's CFL step here (the MIN all-reduce's operand)
-    int *cfl_tickets; // 1 + CFL_TICKET_LANES counters of the "last workgroup folds" scheme (zero between launches)
     // per-ring partial sums of v_phi left by k_source_march for the transport's ring mean
     // (pstride entries per ring, src_ring_nparts of them valid, 0 = not available)
     double *ring_part;

@@ -21,8 +21,7 @@ enum KernelId {
     KID_SRC_FUSED, KID_AV_FUSED, KID_VISC_FUSED, KID_SOURCE_MARCH, KID_THETA_MARCH,
     KID_TRANSPORT_FUSED, KID_MASSFLOW, KID_CFL_RINGS, KID_THETA_GATED_BOUNDARY, KID_EXCHANGE_COPY,
     KID_DISK_ON_BODY, KID_VISC_FACTORS, KID_SOURCE_MARCH_ADI, KID_SOURCE_MARCH_ADI_WIDE,
-    KID_TRANSPORT_FUSED_THERM, KID_TRANSPORT_FUSED_WIDE, KID_STEP_COOP, KID_ACCEL_ON_GAS,
-    KID_SOURCE_MARCH_ADI_ACC, KID_TRANSPORT_RADIAL_MEANS, KID_CFL_RINGS_BC, KID_COUNT
+    KID_ACCEL_ON_GAS, KID_SOURCE_MARCH_ADI_ACC, KID_TRANSPORT_RADIAL_MEANS, KID_CFL_RINGS_BC, KID_COUNT
 };
 static_assert(KID_COUNT <= 64, "fcpt_profile_start selects kernels with a 64-bit mask");
 extern const char *const kKernelNames[KID_COUNT];
@@ -65,7 +64,6 @@ struct TransportResult {
     int marched;  // > 0: a marching kernel ran (new state complete, clock advanced)
     double *sigma, *energy, *vrad, *vazi;
     int split;    // only a part of the chunks was marched
-    int thermal;  // the kernel left the cell-local CFL terms of the new state in Dev::cfl_thermal
     int gated_pending; // launch_transport(defer_gated): the gated azimuthal launch of the fallback is still to be queued (launch_gated_theta)
 };
 // the arguments of that launch, kept by the caller until the final boundary call of the step

@@ -61,7 +61,7 @@ bool enqueue_kick(fcpt_ctx *c, bool fold_bc = false)
             launch_cfl_final(P, 1, st);
         c->fold_pending = false;
         int segs = 0;
-        if (c->march_source && c->skip_q_store && P.adiabatic && cfl_by_rings(P) && !P.cfl_thermal) {
+        if (c->march_source && c->skip_q_store && P.adiabatic && cfl_by_rings(P)) {
             Dev Q = P; // (Q+ and Q- themselves are read by nothing on the device in this configuration: the ring kernel of the CFL reduction takes their difference)
             Q.q_skip = 1;
             segs = launch_source_march(Q, st, fold_bc, &c->kick_bc_folded, fold_cfl);
@@ -190,10 +190,6 @@ void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool spl
     c->want_gated_deferred = false;
     if (!tr.marched)
         launch_clock_advance(P.clk, st);
-    // a marching transport kernel stored the cell-local CFL terms with the new Sigma and e; they stay those of the
-    // final state if nothing but boundary rings and ghost rows changes before the next CFL reduction (the wave
-    // damping folded into that kernel, or no damping zone on this slab)
-    c->thermal_valid = tr.thermal != 0 && tr.marched > 0 && !frog && (!c->damp_any || P.damp_in_step != 0);
     // the marching transport is out of place: the new state may sit in the scratch twins
     if (tr.sigma != c->P.sigma)
         std::swap(c->P.sigma, c->P.sigA);
@@ -276,7 +272,6 @@ void enqueue_post(fcpt_ctx *c, bool may_defer_boundary)
 void enqueue_cfl(fcpt_ctx *c, int apply_policy)
 {
     join_side(c);
-    c->P.cfl_thermal_on = c->thermal_valid ? 1 : 0;
     c->P.qdiff_on = c->qdiff_valid ? 1 : 0;
     if (c->bc_deferred && !c->cfl_interior && cfl_bc_mergeable(c->P)) {
         c->bc_deferred = false;
@@ -308,7 +303,6 @@ int fcpt_cfl_begin(fcpt_ctx *c)
     if (c->P.opt.cfl_split == 0)
         return FCPT_OK;
     ProfScope prof_scope(c);
-    c->P.cfl_thermal_on = c->thermal_valid ? 1 : 0;
     c->P.qdiff_on = c->qdiff_valid ? 1 : 0;
     c->cfl_interior = launch_cfl_interior(c->P, c->stream);
     HIPCHK(hipGetLastError());
@@ -465,8 +459,6 @@ int fcpt_apply_boundary(fcpt_ctx *c, double dt, int32_t final)
     join_side(c);
     ProfScope prof_scope(c);
     launch_clock_set_dt(c->P.clk, dt, c->stream);
-    if (final && c->damp_any)
-        c->thermal_valid = false; // the wave damping changes Sigma and e of the damping zones
     apply_boundary(c, final != 0);
     HIPCHK(hipGetLastError());
     return FCPT_OK;
@@ -479,7 +471,7 @@ unsigned launch_flags(const fcpt_ctx *c)
     return (c->potential_valid ? 1u : 0u) | (c->pressure_valid ? 2u : 0u) | (c->stepped ? 4u : 0u) |
            (c->cfl_interior ? 8u : 0u) | (c->kick_energy_b ? 16u : 0u) | (c->fused_source ? 32u : 0u) |
            (c->march_source ? 64u : 0u) | (c->has_mid ? 128u : 0u) | (c->join_pending ? 256u : 0u) |
-           (c->thermal_valid ? 512u : 0u) | (c->ghosts_unknown ? 1024u : 0u) | (c->qdiff_valid ? 2048u : 0u) |
+           (c->ghosts_unknown ? 1024u : 0u) | (c->qdiff_valid ? 2048u : 0u) |
            (c->bc_deferred ? 4096u : 0u) | ((unsigned)c->src_parts << 13);
 }
 bool graph_wanted(const fcpt_ctx *c)
@@ -549,7 +541,6 @@ bool capture_graph(fcpt_ctx *c, int cycle)
         c->stepped = f0 & 4u;
         c->cfl_interior = f0 & 8u;
         c->kick_energy_b = f0 & 16u;
-        c->thermal_valid = f0 & 512u;
         c->ghosts_unknown = f0 & 1024u;
         c->qdiff_valid = f0 & 2048u;
         c->bc_deferred = f0 & 4096u;

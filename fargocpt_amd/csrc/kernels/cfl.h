@@ -86,8 +86,6 @@ template <bool ROWU> __global__ void k_cfl_cells(const Dev P, double *part, int 
     if (tid == 0)
         part[blockIdx.y * gridDim.x + blockIdx.x] = dmax(dmax(s_w[0], s_w[1]), dmax(s_w[2], s_w[3]));
 }
-__device__ __forceinline__ void cfl_fold(const Dev &P, const double *part, int nparts, int apply_policy);
-__device__ __forceinline__ bool cfl_last_workgroup(int *tickets, int b, int nb);
 // Ring mean and per-cell limits in one pass: a block owns a ring, keeps its v_phi in registers
 // (CFL_MAXP pairs per thread), sums them (<v_phi>, cfl.cpp:196-205), then evaluates the cells of
 // the ring against that mean (:222-330) -- v_phi is read once instead of once by k_ring_mean and
@@ -95,17 +93,16 @@ __device__ __forceinline__ bool cfl_last_workgroup(int *tickets, int b, int nb);
 #define CFL_MAXP 8 // pairs of cells per thread (Nphi <= 4096); 16 for rings up to 8192 cells
 // The launch covers rings [r1, r1+n1) and [r2, r2+n2): all of them in one go, or (slabs with neighbours) the
 // interior while the ghost rings are on the wire and the rings next to them after the unpack (fcpt_cfl_begin).
-// finalize: 0 = partial maxima only (the interior rings ahead of the ghost exchange), 1 + apply_policy = the last
-// workgroup also folds them (cfl_fold over all nr rings)
+// k_cfl_final folds the partial maxima.
 // NT threads per ring, MAXP pairs of cells per thread (NT x MAXP x 2 >= Nphi)
 // (P BY VALUE, as a kernel's own argument: with `const Dev &P` the scheduler hoists the loads of all eight cell pairs of
 //  the 256-thread form -- 224 instead of 100 registers, two instead of four wavefronts per SIMD -- and the ideal-EOS
 //  launch takes 97 instead of 74 us: occupancy beats loads in flight per thread here)
-// HOIST (the 1024-thread forms, two cell pairs per thread): everything else a cell pair needs -- v_r of rings i and i+1,
+// HOIST (the 512-thread forms, four cell pairs per thread): everything else a cell pair needs -- v_r of rings i and i+1,
 // v_phi of cell j+2, and for the ideal EOS e, Sigma, Q+ - Q- -- is loaded TOGETHER with v_phi, ahead of the ring
 // sum and its barrier, which none of it depends on: one memory round trip per workgroup instead of two.
 struct CflPair {
-    D2 r0, r1, e2, s2, qp, qm, th;
+    D2 r0, r1, e2, s2, qp, qm;
     double van1;
 };
 template <bool ADI> __device__ __forceinline__ CflPair cfl_load_pair(const Dev &P, size_t row, int nphi, int j)
@@ -113,11 +110,8 @@ template <bool ADI> __device__ __forceinline__ CflPair cfl_load_pair(const Dev &
     CflPair d;
     d.r0 = *(const D2 *)(P.vrad + row + j), d.r1 = *(const D2 *)(P.vrad + row + nphi + j);
     d.van1 = P.vazi[row + (j + 2 >= nphi ? 0 : j + 2)]; // v_phi of cell j+2
-    d.e2 = D2{0.0, 0.0}, d.s2 = D2{1.0, 1.0}, d.qp = D2{0.0, 0.0}, d.qm = D2{0.0, 0.0}, d.th = D2{0.0, 0.0};
-    const bool thermal = ADI && P.cfl_thermal_on != 0; // invdt1^2 + invdt5^2 + invdt6^2 left by the transport
-    if (thermal) {
-        d.th = *(const D2 *)(P.cfl_thermal + row + j);
-    } else if (ADI) {
+    d.e2 = D2{0.0, 0.0}, d.s2 = D2{1.0, 1.0}, d.qp = D2{0.0, 0.0}, d.qm = D2{0.0, 0.0};
+    if (ADI) {
         d.e2 = *(const D2 *)(P.energy + row + j);
         d.s2 = *(const D2 *)(P.sigma + row + j);
         if (P.qdiff_on) { // Q+ - Q- as one grid, left by the source march
@@ -187,15 +181,14 @@ template <bool ADI, int MAXP, int NT, bool HOIST = false> __device__ __forceinli
             if (p < npair) {
                 const int j = 2 * p;
                 const CflPair d = HOIST ? pd[HOIST ? n : 0] : cfl_load_pair<ADI>(P, row, nphi, j);
-                const D2 r0 = d.r0, r1 = d.r1, e2 = d.e2, s2 = d.s2, qp = d.qp, qm = d.qm, th = d.th;
+                const D2 r0 = d.r0, r1 = d.r1, e2 = d.e2, s2 = d.s2, qp = d.qp, qm = d.qm;
                 const double van1 = d.van1;
-                const bool thermal = ADI && P.cfl_thermal_on != 0;
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     const double vr0 = c ? r0.y : r0.x, vr1 = c ? r1.y : r1.x;
                     const double v = c ? va[n].y : va[n].x, van = c ? van1 : va[n].y;
                     double cs = cs_iso, nu = nu_iso;
-                    if (ADI && !thermal) { // k_adi_cs_h + k_viscosity in registers
+                    if (ADI) { // k_adi_cs_h + k_viscosity in registers
                         const double e = c ? e2.y : e2.x, sg = c ? s2.y : s2.x;
                         cs = sqrt(gg1 * e * fast_rcp(sg));
                         const double H = cs * inv_sqrt_gamma * inv_omk;
@@ -219,15 +212,12 @@ template <bool ADI, int MAXP, int NT, bool HOIST = false> __device__ __forceinli
                     }
                     const double invdt5 = 4.0 * nu * (inv_cell * inv_cell) * lf;
                     double invdt6 = 0.0;
-                    if (ADI && !thermal) {
+                    if (ADI) {
                         const double e = c ? e2.y : e2.x;
                         invdt6 = inv_limit * fabs(((c ? qp.y : qp.x) - (c ? qm.y : qm.x)) * fast_rcp(e)) * lf;
                     }
-                    if (thermal)
-                        s = dmax(s, (c ? th.y : th.x) + invdt2 * invdt2 + invdt3 * invdt3 + invdt4 * invdt4);
-                    else
-                        s = dmax(s, invdt1 * invdt1 + invdt2 * invdt2 + invdt3 * invdt3 + invdt4 * invdt4 +
-                                        invdt5 * invdt5 + invdt6 * invdt6);
+                    s = dmax(s, invdt1 * invdt1 + invdt2 * invdt2 + invdt3 * invdt3 + invdt4 * invdt4 + invdt5 * invdt5 +
+                                    invdt6 * invdt6);
                 }
             }
         }
@@ -246,13 +236,11 @@ template <bool ADI, int MAXP, int NT, bool HOIST = false> __device__ __forceinli
     }
 }
 #define CFL_RINGS_ATTR __launch_bounds__(NT)
-template <bool ADI, int MAXP, int NT = 256> __global__ void CFL_RINGS_ATTR k_cfl_rings(const Dev P, double *part, int r1, int n1, int r2, int finalize)
+template <bool ADI, int MAXP, int NT = 256> __global__ void CFL_RINGS_ATTR k_cfl_rings(const Dev P, double *part, int r1, int n1, int r2)
 {
     const int b = xcd_block(blockIdx.x, gridDim.x); // neighbouring rings share the v_r row between them: same L2
     const int i = b < n1 ? r1 + b : r2 + (b - n1);
     cfl_ring_block<ADI, MAXP, NT, (NT >= 512)>(P, part, i);
-    if (finalize && cfl_last_workgroup(P.cfl_tickets, blockIdx.x, gridDim.x))
-        cfl_fold(P, part, P.nr, finalize - 1);
 }
 // condition_cfl of step n + 1 and the final boundary call of step n (boundary_conditions.cpp:65-114 without its damping,
 // which the transport kernel applied) in ONE launch -- the device-resident loop of fcpt_run_steps, where the two are
@@ -373,34 +361,6 @@ __device__ __forceinline__ double cfl_fold_in_step(const Dev &P)
 __global__ void __launch_bounds__(1024) k_cfl_final(const Dev P, const double *part, int nparts, int apply_policy)
 {
     cfl_fold(P, part, nparts, apply_policy);
-}
-// "Last workgroup folds": every workgroup of k_cfl_rings takes a ticket after its partial maximum is in memory, the
-// one that draws the last ticket runs cfl_fold -- no separate launch for the final fold.  Two levels of tickets
-// (CFL_TICKET_LANES counters, then one) keep the same-address atomics, ~10 ns each on this GPU, off the critical path.
-#define CFL_TICKET_LANES 16
-__device__ __forceinline__ bool cfl_last_workgroup(int *tickets, int b, int nb)
-{
-    __shared__ int s_last;
-    if (threadIdx.x == 0) {
-        const int lane = b % CFL_TICKET_LANES;
-        const int in_lane = nb / CFL_TICKET_LANES + (lane < nb % CFL_TICKET_LANES ? 1 : 0);
-        const int lanes_used = nb < CFL_TICKET_LANES ? nb : CFL_TICKET_LANES;
-        int last = 0;
-        // release: this workgroup's partial result (written by this thread) is visible before the ticket
-        if (__hip_atomic_fetch_add(tickets + 1 + lane, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == in_lane - 1) {
-            tickets[1 + lane] = 0;
-            if (__hip_atomic_fetch_add(tickets, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == lanes_used - 1) {
-                tickets[0] = 0; // ready for the next launch (stream order)
-                last = 1;
-            }
-        }
-        s_last = last;
-    }
-    __syncthreads();
-    const bool last = s_last != 0;
-    if (last)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); // the other workgroups' partials, not this CU's cache
-    return last;
 }
 
 // ---------------------------------------------------------------------------

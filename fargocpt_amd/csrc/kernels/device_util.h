@@ -37,13 +37,8 @@ static inline Launch2D launch2d(int nrows, int nphi)
 // two adjacent doubles moved as one 16-byte access (the address is only 8-byte aligned)
 typedef double D2v __attribute__((ext_vector_type(2)));
 typedef D2v __attribute__((aligned(8))) D2;
-#ifdef EXP_NT
-#define LD2(p_) __builtin_nontemporal_load((const D2 *)(p_))
-#define ST2(p_, v_) __builtin_nontemporal_store((v_), (D2 *)(p_))
-#else
 #define LD2(p_) (*(const D2 *)(p_))
 #define ST2(p_, v_) (*(D2 *)(p_) = (v_))
-#endif
 
 // packed per-ring rows through the constant address space (wide scalar loads)
 template <class T> __device__ __forceinline__ T crow_load(const T *tab, int i)

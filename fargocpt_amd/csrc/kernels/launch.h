@@ -12,7 +12,7 @@ const char *const kKernelNames[KID_COUNT] = {
     "k_cfl_cells", "k_clock", "k_src_fused", "k_av_fused", "k_visc_fused", "k_source_march",
     "k_transport_theta_march", "k_transport_fused", "k_massflow", "k_cfl_rings", "k_theta_march_gated_boundary",
     "k_exchange_copy", "k_disk_on_body", "k_visc_factors", "k_source_march_adi", "k_source_march_adi_wide",
-    "k_transport_fused_therm", "k_transport_fused_wide", "k_step_coop", "k_accel_on_gas", "k_source_march_adi_acc",
+    "k_accel_on_gas", "k_source_march_adi_acc",
     "k_transport_radial_means", "k_cfl_rings_bc"};
 
 thread_local Profiler *g_prof = nullptr;
@@ -287,10 +287,9 @@ static std::vector<int> transport_chunk_list(const Dev &P, const std::vector<int
     std::vector<int> out;
     if (P.nphi < 256 || P.opt.transport_rows > 0 || P.opt.transport_graded == 0)
         return out;
-    if (P.opt.transport_fused == 0 || P.opt.transport_fused == 2)
+    if (P.opt.transport_fused == 0)
         return out;
-    const int tstride = 64 - (TfHalo<1>::lo + TfHalo<1>::hi);
-    const long tiles = (P.nphi + tstride - 1) / tstride;
+    const long tiles = (P.nphi + TF_STRIDE - 1) / TF_STRIDE;
     const long slots = (long)device_cus() * 4 * 4; // 4 wavefronts per SIMD (128 VGPRs)
     const double conc = (double)slots / (double)tiles; // chunks resident at once
     const bool explicit_spec = lengths && !lengths->empty(); // fcpt_set_transport_chunks / FCPT_TF_SCHEDULE: tuning runs and tests
@@ -358,8 +357,7 @@ static std::vector<int> transport_rank_table(const Dev &P, const std::vector<int
     std::vector<int> out;
     if (P.opt.transport_rank_grade == 0)
         return out;
-    const int tstride = 64 - (TfHalo<1>::lo + TfHalo<1>::hi);
-    const int tiles = (P.nphi + tstride - 1) / tstride;
+    const int tiles = (P.nphi + TF_STRIDE - 1) / TF_STRIDE;
     const int occ = 4, PRE = 5;
     const int wpr = device_cus() / 8 * 4; // wavefronts of one rank in an XCD: one per SIMD
     const int rows = P.nr;
@@ -427,7 +425,7 @@ static std::vector<int> transport_rank_table(const Dev &P, const std::vector<int
 std::vector<int> transport_schedule(const Dev &P, const std::vector<int> &slow, const std::vector<int> *lengths)
 {
     std::vector<int> out;
-    if (P.nphi < 256 || P.opt.transport_rows > 0 || P.opt.transport_fused == 0 || P.opt.transport_fused == 2)
+    if (P.nphi < 256 || P.opt.transport_rows > 0 || P.opt.transport_fused == 0)
         return out;
     const std::vector<int> chunks = transport_chunk_list(P, slow, lengths);
     if (chunks.empty()) {
@@ -435,15 +433,13 @@ std::vector<int> transport_schedule(const Dev &P, const std::vector<int> &slow, 
         if (explicit_spec || P.opt.transport_graded == 0)
             return out;
         // one round of equal chunks?
-        const int tstride = 64 - (TfHalo<1>::lo + TfHalo<1>::hi);
-        const long tiles = (P.nphi + tstride - 1) / tstride;
+        const long tiles = (P.nphi + TF_STRIDE - 1) / TF_STRIDE;
         const int rows_u = transport_rows(P);
         if ((long)((P.nr + rows_u - 1) / rows_u) * tiles > (long)device_cus() * 4 * 4)
             return out;
         return transport_rank_table(P, slow);
     }
-    const int tstride = 64 - (TfHalo<1>::lo + TfHalo<1>::hi);
-    const int tiles = (P.nphi + tstride - 1) / tstride;
+    const int tiles = (P.nphi + TF_STRIDE - 1) / TF_STRIDE;
     const int count = (int)(chunks.size() / 2);
     // as the kernel deals equal chunks: workgroup b runs on XCD b % 8; chunk c on XCD c % 8, its tiles side by side
     const int nblk = 8 * ((((count + 7) / 8) * tiles + 3) / 4);
@@ -486,9 +482,7 @@ static int transport_rows(const Dev &P)
 {
     if (P.opt.transport_rows > 0)
         return P.opt.transport_rows;
-    const int CF = 1; // cells per lane of the default kernel
-    const int tstride = 64 * CF - (TfHalo<1>::lo + TfHalo<1>::hi);
-    const long tiles = (P.nphi + tstride - 1) / tstride;
+    const long tiles = (P.nphi + TF_STRIDE - 1) / TF_STRIDE;
     const long slots_xcd = (long)device_cus() / 8 * 4 * 4; // 4 wavefronts per SIMD (128 VGPRs)
     const double slow = P.damp_in_step ? 1.5 : 1.0;
     int r = 4;
@@ -809,8 +803,8 @@ bool transport_can_split(const Dev &P, bool shear_safe)
         return false;
     if (P.opt.transport_fallback != 0)
         return false; // the fallback kernels behind the fused one need all of its chunks in one launch
-    if (P.opt.transport_fused >= 0 || P.opt.transport_rows > 0)
-        return false; // tuning runs keep the one-launch form
+    if (P.opt.transport_fused == 0 || P.opt.transport_rows > 0)
+        return false; // no fused kernel / tuning runs keep the one-launch form
     if (P.opt.transport_split == 0)
         return false;
     const int rows = transport_rows(P);
@@ -825,16 +819,11 @@ TransportResult launch_transport(const Dev &P, const Dev &W, hipStream_t st, int
 {
     // P: view whose vrad/vazi are the velocities to transport; W: view that receives the new state
     // Transport, TransportEuler.cpp:112-136
-    TransportResult res = {0, W.sigma, W.energy, W.vrad, W.vazi, 0, 0, 0};
-    // ---- everything in one kernel (tiled rings only) ------------------------------------------
-    int CF = P.nphi >= 256 ? 1 : 0; // 1 cell per lane: 3 waves per SIMD (2 cells: 284 VGPRs, 1 wave)
-    if (P.opt.transport_fused >= 0) { // 0: off, 1 / 2: cells per lane
-        const int v = P.opt.transport_fused;
-        CF = v == 0 ? 0 : ((v == 1 || v == 2) && P.nphi >= 128 * v ? v : CF);
-    }
-    if ((long long)(P.nr + 1) * P.nphi >= (1ll << 29))
-        CF = 0; // the fused kernel addresses its grids with 32-bit byte offsets (4 GiB each)
-    if (CF) {
+    TransportResult res = {0, W.sigma, W.energy, W.vrad, W.vazi, 0, 0};
+    // ---- everything in one kernel (tiled rings only; option transport_fused = 0: off) -----------
+    // (the fused kernel addresses its grids with 32-bit byte offsets, 4 GiB each)
+    const bool fused = P.nphi >= 256 && P.opt.transport_fused != 0 && (long long)(P.nr + 1) * P.nphi < (1ll << 29);
+    if (fused) {
         Dev Wm = W; // the marching kernels cannot work in place
         Wm.sigma = W.sigA;
         Wm.energy = W.eA;
@@ -843,8 +832,7 @@ TransportResult launch_transport(const Dev &P, const Dev &W, hipStream_t st, int
         if (part == TRANSPORT_ALL)
             launch_shift_means(P, st); // else: the caller queued it ahead of both parts
         const int rows = transport_rows(P);
-        const int tstride = 64 * CF - (CF == 2 ? TfHalo<2>::lo + TfHalo<2>::hi : TfHalo<1>::lo + TfHalo<1>::hi);
-        const int tiles = (P.nphi + tstride - 1) / tstride;
+        const int tiles = (P.nphi + TF_STRIDE - 1) / TF_STRIDE;
         const int chunks = (P.nr + rows - 1) / rows;
         // The azimuthal half of the two-kernel transport is always queued behind the fused kernel (one idle launch) and
         // runs only if a ring pair exceeds the one-lane shift.  The CFL condition's shear limit
@@ -854,7 +842,7 @@ TransportResult launch_transport(const Dev &P, const Dev &W, hipStream_t st, int
         // for flows known to be benign; a violation is then reported as FCPT_ESHEAR.
         const int fallback = P.opt.transport_fallback != 0;
         TfChunks ch = {chunks, chunks, 0, 1, nullptr};
-        const bool sched = part == TRANSPORT_ALL && P.tf_sched_n > 0 && P.opt.transport_rows <= 0 && CF == 1;
+        const bool sched = part == TRANSPORT_ALL && P.tf_sched_n > 0 && P.opt.transport_rows <= 0;
         if (sched)
             ch = TfChunks{P.tf_sched_n, P.tf_sched_n, 0, 1, P.tf_sched};
         const int c_lo = (P.nr - 2 * FCPT_OVERLAP) / rows;    // first chunk of the outer tail (holds row nr - 14)
@@ -868,41 +856,25 @@ TransportResult launch_transport(const Dev &P, const Dev &W, hipStream_t st, int
         const dim3 grid(sched ? (ch.count + 3) / 4
                               : (ch.count >= TF_XCD_CHUNKS ? 8 * ((((ch.count + 7) / 8) * tiles + 3) / 4) : (ch.count * tiles + 3) / 4)),
             block(256);
-#define TFK2(ID, KK, CC, AA, DD)                                                                    \
-    if (P.limiter == FCPT_LIMITER_MC)                                                                \
-        KLAUNCH(ID, (KK<CC, AA, DD, FCPT_LIMITER_MC>), grid, block, P, Wm, tiles, rows, fallback, ch); \
-    else                                                                                             \
-        KLAUNCH(ID, (KK<CC, AA, DD, FCPT_LIMITER_VANLEER>), grid, block, P, Wm, tiles, rows, fallback, ch)
-#define TFK(CC, AA, DD)                                \
-    if (CC == 1 && AA && Wm.cfl_thermal) {             \
-        TFK2(KID_TRANSPORT_FUSED_THERM, k_transport_fused_therm, 1, true, DD); \
-    } else if (CC == 1) {                              \
-        TFK2(KID_TRANSPORT_FUSED, k_transport_fused, 1, AA, DD); \
-    } else {                                           \
-        TFK2(KID_TRANSPORT_FUSED_WIDE, k_transport_fused_wide, 2, AA, DD); \
-    }
-#define TFC(CC)                    \
-    if (P.adiabatic) {             \
-        if (W.damp_in_step) {      \
-            TFK(CC, true, true)    \
-        } else {                   \
-            TFK(CC, true, false)   \
-        }                          \
-    } else {                       \
-        if (W.damp_in_step) {      \
-            TFK(CC, false, true)   \
-        } else {                   \
-            TFK(CC, false, false)  \
-        }                          \
-    }
-        if (CF == 2) {
-            TFC(2)
+#define TFK(AA, DD)                                                                                              \
+    if (P.limiter == FCPT_LIMITER_MC)                                                                              \
+        KLAUNCH(KID_TRANSPORT_FUSED, (k_transport_fused<AA, DD, FCPT_LIMITER_MC>), grid, block, P, Wm, tiles, rows, fallback, ch); \
+    else                                                                                                           \
+        KLAUNCH(KID_TRANSPORT_FUSED, (k_transport_fused<AA, DD, FCPT_LIMITER_VANLEER>), grid, block, P, Wm, tiles, rows, fallback, ch)
+        if (P.adiabatic) {
+            if (W.damp_in_step) {
+                TFK(true, true);
+            } else {
+                TFK(true, false);
+            }
         } else {
-            TFC(1)
+            if (W.damp_in_step) {
+                TFK(false, true);
+            } else {
+                TFK(false, false);
+            }
         }
-#undef TFC
 #undef TFK
-#undef TFK2
         // behind it, the azimuthal march of the two-kernel form: its blocks return at once unless k_ring_mean met
         // |Nshift[i] - Nshift[i-1]| > 1 (a time step beyond the FARGO shear limit) -- the fused launch then ran the
         // radial sweep.  (Round 2 did both sweeps in this second launch with a hand-rolled grid barrier between them;
@@ -915,7 +887,6 @@ TransportResult launch_transport(const Dev &P, const Dev &W, hipStream_t st, int
             launch_theta_march(P, Wm, 2, 0, 0, P.shift_jump, st);
         }
         res.marched = tiles;
-        res.thermal = CF == 1 && P.adiabatic && Wm.cfl_thermal != nullptr;
         res.sigma = Wm.sigma, res.energy = Wm.energy, res.vrad = Wm.vrad, res.vazi = Wm.vazi;
         return res;
     }
@@ -934,8 +905,8 @@ TransportResult launch_transport(const Dev &P, const Dev &W, hipStream_t st, int
     ThetaOut outA = {P.rmpA, P.rmmA, P.lpA, P.lmA, P.sigA, P.eA};
     ThetaSet inA = {P.rmpA, P.rmmA, P.lpA, P.lmA, P.sigA, P.eA};
     ThetaOut outB = {P.rmpB, P.rmmB, P.lpB, P.lmB, P.sigB, P.eB};
-    // ring-marching azimuthal kernel when a lane-chunk size fits the ring, else (and with FCPT_THETA_MARCH=0 or
-    // FCPT_THETA_FUSED=0) the per-pass kernels
+    // ring-marching azimuthal kernel when a lane-chunk size fits the ring, else (and with FCPT_THETA_MARCH=0) the
+    // per-pass kernels
     int C = 0, periodic = 0;
     for (int c : {1, 2, 4})
         if (!C && P.nphi % c == 0 && P.nphi <= 64 * c && (c == 1 || P.nphi / c >= 1)) {
@@ -944,8 +915,6 @@ TransportResult launch_transport(const Dev &P, const Dev &W, hipStream_t st, int
         }
     if (!C && P.nphi > 64 * 2)
         C = 2;
-    if (P.opt.theta_fused == 0)
-        C = 0;
     const bool march = C != 0 && P.opt.theta_march != 0;
     if (march) {
         // the kernel reads the pre-transport v_phi and v_r of a ring (halo columns included) while other
@@ -955,7 +924,6 @@ TransportResult launch_transport(const Dev &P, const Dev &W, hipStream_t st, int
         Wm.vrad = P.vrad == W.vrad ? W.vrad_b : W.vrad;
         Wm.vazi = P.vazi == W.vazi ? W.vazi_b : W.vazi;
         res.marched = launch_theta_march(P, Wm, C, periodic, 1, nullptr, st);
-        res.thermal = P.adiabatic && Wm.cfl_thermal != nullptr;
         res.vrad = Wm.vrad, res.vazi = Wm.vazi;
     } else {
         LAUNCH2D_T(KID_THETA1, k_transport_theta, 1, P.nr, P, inB, outA);
@@ -1001,52 +969,36 @@ bool cfl_by_rings(const Dev &P)
     return (P.nphi & 1) == 0 && P.nphi >= 128 && P.nphi <= 1024 * CFL_MAXP && (!P.adiabatic || P.lazy_derived) &&
            P.stabilize != 2 && P.opt.cfl_rings != 0;
 }
-// rings of 2049 .. 4096 cells: 1024 threads with two cell pairs each and ALL their loads ahead of the ring sum, instead
-// of 256 with eight.  Isothermal (two grids): 37 -> 33 us at 2048 x 4096 (profiles/r03_ab_cfl_threads.txt).  Ideal EOS
-// (five grids, 100 VGPRs = one 1024-thread workgroup per CU): 65 against 52 us in the bench's units, 0.505-0.508
-// against 0.491-0.496 ms per step (profiles/r03_ab_cfl_hoist.txt) -- it keeps the 256-thread form.
-// (round 3, later: 512 threads with four pairs each read 22.7-23.6 us where 1024 with two read 23.8-25.6, the step
-//  0.3187 against 0.3197 ms, three A/B pairs, profiles/r03_ab_cfl_512.txt: the isothermal built-in; ideal EOS 62-65 us
-//  against 56 for its 256-thread form)
-static int cfl_block_form(const Dev &P) // 0: 256 threads per ring, 1: 1024, 2: 512 (the wide forms load everything ahead of the ring sum)
+// rings of 2049 .. 4096 cells: 512 threads with four cell pairs each and ALL their loads ahead of the ring sum, instead
+// of 256 with eight.  Isothermal (two grids): 22.7-23.6 us at 2048 x 4096, the step 0.3187 ms, against 37 us for the
+// 256-thread form and 23.8-25.6 us / 0.3197 ms for 1024 threads with two pairs each (three A/B pairs,
+// profiles/r03_ab_cfl_threads.txt, r03_ab_cfl_512.txt).  Ideal EOS (five grids): 62-65 us against 56 for the 256-thread
+// form, which it keeps (profiles/r03_ab_cfl_hoist.txt).
+// cfl_wide_blocks: -1 = built-in (isothermal 512 threads, ideal EOS 256), 0 = 256, any other value = 512
+static bool cfl_wide_blocks(const Dev &P)
 {
-    return P.opt.cfl_wide_blocks < 0 ? (P.adiabatic ? 0 : 2) : P.opt.cfl_wide_blocks;
+    return P.opt.cfl_wide_blocks < 0 ? !P.adiabatic : P.opt.cfl_wide_blocks != 0;
 }
-static bool cfl_wide_blocks(const Dev &P) { return cfl_block_form(P) != 0; }
-static void launch_cfl_rings(const Dev &P, int r1, int n1, int r2, int n2, int finalize, hipStream_t st)
+static void launch_cfl_rings(const Dev &P, int r1, int n1, int r2, int n2, hipStream_t st)
 {
     if (n1 + n2 <= 0)
         return;
     const bool wide = P.nphi > 512 * CFL_MAXP;
-#ifdef FCPT_CFL_NT /* tuning builds: NT threads per ring, CFL_MAXP * 256 / NT pairs each (Nphi <= 4096) */
-    if (!wide) {
+    if (!wide && P.nphi > 2048 && cfl_wide_blocks(P)) { // 512 threads with four cell pairs each
         if (P.adiabatic)
-            KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<true, CFL_MAXP * 256 / FCPT_CFL_NT, FCPT_CFL_NT>), dim3(n1 + n2), dim3(FCPT_CFL_NT), P, P.cfl_part, r1, n1, r2, finalize);
+            KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<true, CFL_MAXP / 2, 512>), dim3(n1 + n2), dim3(512), P, P.cfl_part, r1, n1, r2);
         else
-            KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<false, CFL_MAXP * 256 / FCPT_CFL_NT, FCPT_CFL_NT>), dim3(n1 + n2), dim3(FCPT_CFL_NT), P, P.cfl_part, r1, n1, r2, finalize);
-        return;
-    }
-#endif
-    if (!wide && P.nphi > 2048 && cfl_wide_blocks(P)) {
-        if (cfl_block_form(P) == 2) { // 512 threads with four cell pairs each
-            if (P.adiabatic)
-                KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<true, CFL_MAXP / 2, 512>), dim3(n1 + n2), dim3(512), P, P.cfl_part, r1, n1, r2, finalize);
-            else
-                KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<false, CFL_MAXP / 2, 512>), dim3(n1 + n2), dim3(512), P, P.cfl_part, r1, n1, r2, finalize);
-        } else if (P.adiabatic)
-            KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<true, CFL_MAXP / 4, 1024>), dim3(n1 + n2), dim3(1024), P, P.cfl_part, r1, n1, r2, finalize);
-        else
-            KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<false, CFL_MAXP / 4, 1024>), dim3(n1 + n2), dim3(1024), P, P.cfl_part, r1, n1, r2, finalize);
+            KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<false, CFL_MAXP / 2, 512>), dim3(n1 + n2), dim3(512), P, P.cfl_part, r1, n1, r2);
         return;
     }
     if (P.adiabatic && wide)
-        KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<true, 2 * CFL_MAXP>), dim3(n1 + n2), dim3(256), P, P.cfl_part, r1, n1, r2, finalize);
+        KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<true, 2 * CFL_MAXP>), dim3(n1 + n2), dim3(256), P, P.cfl_part, r1, n1, r2);
     else if (P.adiabatic)
-        KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<true, CFL_MAXP>), dim3(n1 + n2), dim3(256), P, P.cfl_part, r1, n1, r2, finalize);
+        KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<true, CFL_MAXP>), dim3(n1 + n2), dim3(256), P, P.cfl_part, r1, n1, r2);
     else if (wide)
-        KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<false, 2 * CFL_MAXP>), dim3(n1 + n2), dim3(256), P, P.cfl_part, r1, n1, r2, finalize);
+        KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<false, 2 * CFL_MAXP>), dim3(n1 + n2), dim3(256), P, P.cfl_part, r1, n1, r2);
     else
-        KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<false, CFL_MAXP>), dim3(n1 + n2), dim3(256), P, P.cfl_part, r1, n1, r2, finalize);
+        KLAUNCH(KID_CFL_RINGS, (k_cfl_rings<false, CFL_MAXP>), dim3(n1 + n2), dim3(256), P, P.cfl_part, r1, n1, r2);
 }
 // launch_cfl with the final boundary call of the previous step inside the ring launch (see k_cfl_rings_bc); the caller
 // has checked cfl_bc_mergeable()
@@ -1065,16 +1017,10 @@ void launch_cfl_bc(const Dev &P, int apply_policy, hipStream_t st)
     KLAUNCH(KID_CFL_RINGS_BC, (k_cfl_rings_bc<ADI_, MAXP_, NT_>), dim3((P.nphi + NT_ - 1) / NT_ + P.nr), dim3(NT_), P, P.cfl_part, \
             (P.nphi + NT_ - 1) / NT_)
     if (!wide && P.nphi > 2048 && cfl_wide_blocks(P)) {
-        if (cfl_block_form(P) == 2) {
-            if (P.adiabatic) {
-                CFLBC(true, CFL_MAXP / 2, 512);
-            } else {
-                CFLBC(false, CFL_MAXP / 2, 512);
-            }
-        } else if (P.adiabatic) {
-            CFLBC(true, CFL_MAXP / 4, 1024);
+        if (P.adiabatic) {
+            CFLBC(true, CFL_MAXP / 2, 512);
         } else {
-            CFLBC(false, CFL_MAXP / 4, 1024);
+            CFLBC(false, CFL_MAXP / 2, 512);
         }
     } else if (P.adiabatic && wide) {
         CFLBC(true, 2 * CFL_MAXP, 256);
@@ -1099,19 +1045,19 @@ bool launch_cfl_interior(const Dev &P, hipStream_t st)
 {
     if (!cfl_by_rings(P) || P.nr <= CFL_EDGE_LO + CFL_EDGE_HI)
         return false;
-    launch_cfl_rings(P, CFL_EDGE_LO, P.nr - CFL_EDGE_LO - CFL_EDGE_HI, 0, 0, 0, st);
+    launch_cfl_rings(P, CFL_EDGE_LO, P.nr - CFL_EDGE_LO - CFL_EDGE_HI, 0, 0, st);
     return true;
 }
 void launch_cfl(const Dev &P, int apply_policy, hipStream_t st, bool interior_done)
 {
     if (cfl_by_rings(P)) {
-        // (finalize = 0: the final fold as its own small launch.  Letting the last workgroup of k_cfl_rings do it --
-        // cfl_last_workgroup, one agent-scope release per workgroup -- was measured at 110 instead of 36 + 6 us: on
-        // this GPU a device-scope release writes the XCD's L2 back, 2048 times per launch.)
+        // (the final fold as its own small launch.  Letting the last workgroup of k_cfl_rings do it, with one
+        // agent-scope release per workgroup, was measured at 110 instead of 36 + 6 us: on this GPU a device-scope
+        // release writes the XCD's L2 back, 2048 times per launch.)
         if (interior_done)
-            launch_cfl_rings(P, 0, CFL_EDGE_LO, P.nr - CFL_EDGE_HI, CFL_EDGE_HI, 0, st);
+            launch_cfl_rings(P, 0, CFL_EDGE_LO, P.nr - CFL_EDGE_HI, CFL_EDGE_HI, st);
         else
-            launch_cfl_rings(P, 0, P.nr, 0, 0, 0, st);
+            launch_cfl_rings(P, 0, P.nr, 0, 0, st);
         if (apply_policy != 2) // (2: the marching source kernel queued next folds for itself)
             KLAUNCH(KID_CFL_INIT, k_cfl_final, dim3(1), dim3(1024), P, (const double *)P.cfl_part, P.nr, apply_policy);
         return;

@@ -34,19 +34,9 @@
 #endif
 // byte offset of cell (ring r_, this lane's column) in a grid: 32-bit (see ld_off)
 #define MOFF(r_) (((unsigned)(r_) * (unsigned)nphi + (unsigned)j) * 8u)
-#ifndef ADI_OFF32
-#define ADI_OFF32 1 /* loads only: with the stores in this form too the 128-register kernel spills 12 bytes and loses 14 us */
-#endif
-#if ADI_OFF32 & 1
+// loads by 32-bit offset, stores by index: with the stores by offset too the 128-register kernel spills 12 bytes and loses 14 us
 #define ADI_LD(g_, r_) ld_off(g_, MOFF(r_))
-#else
-#define ADI_LD(g_, r_) (g_)[IDX(r_, j)]
-#endif
-#if ADI_OFF32 & 2
-#define ADI_ST(g_, r_, v_) st_off(g_, MOFF(r_), v_)
-#else
 #define ADI_ST(g_, r_, v_) (g_)[IDX(r_, j)] = (v_)
-#endif
 #define MARCH_VALID 59
 #define MARCH_LO 3
 

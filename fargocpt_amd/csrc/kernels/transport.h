@@ -21,35 +21,6 @@ __device__ __forceinline__ double limiter(int type, double a, double b)
     return ab > 0.0 ? 2.0 * ab * fast_rcp1(a + b) : 0.0;
 }
 
-// The cell-local part of the ideal-EOS CFL sum (cfl.cpp:243-247,319-328): invdt1^2 + invdt5^2 + invdt6^2 -- sound
-// speed, viscosity and |Q+ - Q-| / e -- depends on Sigma, e, Q+ and Q- of the cell alone.  The marching transport
-// kernels hold the cell's final Sigma and e when they store them, so they leave that sum in one grid (cfl_thermal)
-// and the next k_cfl_rings reads it instead of Sigma, e, Q+ and Q- (3 grids instead of 6).  c_s^2 = gamma (gamma-1)
-// e / Sigma and nu = alpha H c_s = alpha c_s^2 / (sqrt(gamma) Omega_K) need no root.
-struct ThermalRing {
-    double inv_cell2, nu_fac, lf, inv_limit;
-};
-__device__ __forceinline__ ThermalRing thermal_ring(const Dev &P, int i)
-{
-    ThermalRing t;
-    const double inv_dxr = P.InvDiffRsup[i], inv_dxa = P.InvRmed[i] * P.invdphi;
-    const double inv_cell = dmax(inv_dxr, inv_dxa);
-    t.inv_cell2 = inv_cell * inv_cell;
-    t.nu_fac = P.alpha * (1.0 / sqrt(P.gamma)) * P.g_inv_omk[i];
-    t.lf = P.leapfrog ? 0.6 : 1.0;
-    t.inv_limit = 1.0 / P.heating_cooling_cfl_limit;
-    return t;
-}
-__device__ __forceinline__ double cfl_thermal_term(const Dev &P, const ThermalRing &t, double sg, double e, double qp, double qm)
-{
-    const double re = fast_rcp(e);
-    const double cs2 = P.gamma * (P.gamma - 1.0) * e * fast_rcp(sg);
-    const double nu = P.alpha_viscosity ? t.nu_fac * cs2 : P.nu_const;
-    const double invdt5 = 4.0 * nu * t.inv_cell2 * t.lf;
-    const double invdt6 = t.inv_limit * fabs((qp - qm) * re) * t.lf;
-    return cs2 * t.inv_cell2 + invdt5 * invdt5 + invdt6 * invdt6;
-}
-
 // Upwind "star" state at radial interface k (between rings k-1 and k),
 // compute_star_radial (TransportEuler.cpp:349-406).  wm2..wp1 = Q at rings k-2..k+1.
 // Per-interface geometry of compute_star_radial, loaded once with the (wavefront-uniform)
@@ -550,7 +521,7 @@ template <bool DAMP, bool ROWU> __global__ void k_velocities(const Dev P, ThetaS
 
 // ---------------------------------------------------------------------------
 // Azimuthal transport + velocities + floors + wave damping in ONE kernel, marching over rings.
-// As k_transport_theta_fused, but a wavefront owns a phi segment in POST-shift coordinates and
+// A wavefront owns a phi segment in POST-shift coordinates and
 // walks THETA_ROWS rings outward: for ring i it reads the cells that the integer shift maps
 // onto its segment (input index = output index - Nshift[i]), runs both passes in registers,
 // and -- because ring i-1 was processed by the same lanes one iteration earlier -- forms
@@ -559,7 +530,7 @@ template <bool DAMP, bool ROWU> __global__ void k_velocities(const Dev P, ThetaS
 // applies the density floor / temperature range (:121-131) and the reference/zero wave damping
 // of the final boundary call, and stores the new state.  The transported momenta never go to
 // memory: the sweep reads 6 (7) grids and writes 3 (4) instead of 11 + 8 (13 + 10) doubles per
-// cell for k_transport_theta_fused + k_velocities.
+// cell for a one-launch azimuthal sweep + k_velocities.
 // Validity: 4 cells at either end of a segment are lost to the two passes, one more on the
 // left to the L+(j-1) neighbour.
 #define THETA_ROWS 8
@@ -791,20 +762,13 @@ __device__ __forceinline__ void transport_theta_march_block(const Dev &P, const 
         const double dxtheta = P.g_dxtheta[i];
         const double invdx = P.g_inv_dxtheta[i];
         const double geo_dt = P.g_dr_invsurf[i] * dt;
-#ifndef EXP_THETA_NOCOMP
         theta_pass<C, ADI, PER, 0>(lim, lsrc_l, lsrc_r, geo_dt, dxtheta, invdx, dt, V, 0.0, S, Q, E);
-#else
-#pragma unroll
-        for (int c = 0; c < C; ++c) { Q[1][c] += Q[0][c] * 1e-9; Q[3][c] += (Q[2][c] + V[c]) * 1e-9; }
-#endif
-#ifndef EXP_THETA_NOCOMP
         if (P.fast_transport) {
             if (vconst * dt > 0.0)
                 theta_pass<C, ADI, PER, 1>(lim, lsrc_l, lsrc_r, geo_dt, dxtheta, invdx, dt, V, vconst, S, Q, E);
             else
                 theta_pass<C, ADI, PER, 2>(lim, lsrc_l, lsrc_r, geo_dt, dxtheta, invdx, dt, V, vconst, S, Q, E);
         }
-#endif
         // compute_velocities_from_momenta + floors + damping for ring i (rings < r0 only prime rmp/S)
         if (i >= r0) {
             const double lp_l = SH_PREV(Q[2][C - 1]); // L+ and Sigma of cell j-1
@@ -834,15 +798,6 @@ __device__ __forceinline__ void transport_theta_march_block(const Dev &P, const 
                         e = damp_value(P, e, ten, fs, ts, dt, P.energy0, g, 0.0);
                 }
                 o_vr[c] = vr, o_va[c] = va, o_s[c] = sf, o_e[c] = e;
-            }
-            if (ADI && P.cfl_thermal) {
-                const ThermalRing tr = thermal_ring(P, i);
-#pragma unroll
-                for (int c = 0; c < C; ++c)
-                    if (valid[c]) {
-                        const int g = row + jout[c];
-                        P.cfl_thermal[g] = cfl_thermal_term(P, tr, o_s[c], o_e[c], P.qplus[g], P.qminus[g]);
-                    }
             }
             if (pair_out) { // both cells of the lane are final and adjacent in memory
                 if (valid[0]) {

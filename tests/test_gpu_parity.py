@@ -94,10 +94,10 @@ def test_tiled_azimuthal_sweep_32x640(product, oracle):
 
 
 def test_unfused_paths_agree(product, oracle, monkeypatch):
-    """The per-loop kernels (FCPT_FUSED_SOURCE=0, FCPT_THETA_FUSED=0) stay available as a
+    """The per-loop kernels (FCPT_FUSED_SOURCE=0, FCPT_THETA_MARCH=0) stay available as a
     cross-check of the fused ones."""
     monkeypatch.setenv("FCPT_FUSED_SOURCE", "0")
-    monkeypatch.setenv("FCPT_THETA_FUSED", "0")
+    monkeypatch.setenv("FCPT_THETA_MARCH", "0")
     d = setups.planet_disk(product, 48, 96, adiabatic=True)
     _check(run_pair(product, oracle, d, 20), ("sigma", "vrad", "vazi", "energy"))
 
@@ -201,11 +201,11 @@ def test_boundary_damping_grid_variants(product, oracle, case):
 
 
 FUSED_CASES = ["iso_tw", "iso_sn_mc", "iso_noav_constnu_standard", "adiabatic", "adiabatic_sn", "outflow_zeroshear",
-               "reference_bc_damp_zero", "no_damping", "arithmetic_odd", "three_slabs", "leapfrog", "two_cells_per_lane"]
+               "reference_bc_damp_zero", "no_damping", "arithmetic_odd", "three_slabs", "leapfrog"]
 
 
 @pytest.mark.parametrize("case", FUSED_CASES)
-def test_fused_transport_variants(product, oracle, case, monkeypatch):
+def test_fused_transport_variants(product, oracle, case):
     """k_transport_fused (radial + azimuthal transport + velocities in one marching kernel) takes
     rings of Nphi >= 256: every physics / boundary / grid variant of the path at such sizes."""
     d = setups.planet_disk(product, 44, 320, adiabatic=case.startswith("adiabatic"))
@@ -236,8 +236,6 @@ def test_fused_transport_variants(product, oracle, case, monkeypatch):
         kw["nslabs"] = (3, 1)
     elif case == "leapfrog":
         d.integrator = B.INTEGRATOR_LEAPFROG
-    elif case == "two_cells_per_lane":
-        monkeypatch.setenv("FCPT_TRANSPORT_FUSED", "2")
     _check(run_pair(product, oracle, d, 25, bodies=setups.jupiter_bodies(d), **kw), fields)
 
 
@@ -807,11 +805,9 @@ def test_heating_grids_after_the_device_loop(product):
 
 
 @pytest.mark.parametrize("nslabs", [1, 2])
-def test_cfl_thermal_option(product, oracle, nslabs, monkeypatch):
-    """Option cfl_thermal (off by default: measured slower at 2048 x 4096): the marching transport stores the
-    cell-local part of the ideal-EOS CFL sum with the new state and k_cfl_rings reads it instead of Sigma, e, Q+, Q-.
-    Same dt history and fields as the oracle, on one slab and on two."""
-    monkeypatch.setenv("FCPT_CFL_THERMAL", "1")
+def test_ideal_eos_march_with_planet(product, oracle, nslabs):
+    """Ideal EOS with a planet at 80 x 320: the marching source and transport kernels and k_cfl_rings reading Sigma, e
+    and Q+ - Q-.  Same dt history and fields as the oracle, on one slab and on two."""
     d = setups.planet_disk(product, 80, 320, adiabatic=True)
     _check(run_pair(product, oracle, d, 25, bodies=setups.jupiter_bodies(d), nslabs=(nslabs, 1)), ("sigma", "vrad", "vazi", "energy"))
 

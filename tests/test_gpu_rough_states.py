@@ -19,7 +19,7 @@ TOL = 1e-10
 TOL_DT = 1e-12
 
 SOURCE_MARCH = ("k_source_march", "k_source_march_adi", "k_source_march_adi_wide", "k_source_march_adi_acc")
-TRANSPORT_FUSED = ("k_transport_fused", "k_transport_fused_therm", "k_transport_fused_wide")
+TRANSPORT_FUSED = ("k_transport_fused",)
 TRANSPORT_TWO = ("k_transport_radial", "k_transport_radial_means")
 CFL_RINGS = ("k_cfl_rings", "k_cfl_rings_bc")
 
@@ -89,7 +89,7 @@ def _assert_paths(name, opt, prof, fell):
     else:
         assert ran(SOURCE_MARCH) == 0, f"{name}: a marching source kernel ran on a per-loop case: {sorted(prof)}"
     if opt["tr"] in ("fused", "fallback"):
-        assert ran(TRANSPORT_FUSED) > 0, f"{name}: k_transport_fused* did not run: {sorted(prof)}"
+        assert ran(TRANSPORT_FUSED) > 0, f"{name}: k_transport_fused did not run: {sorted(prof)}"
         if opt["tr"] == "fused":
             # the fallback's azimuthal launch is queued behind every fused one and returns at once unless the
             # shift-jump stamp is raised: the stamp, not the launch count, says whether it computed the step
