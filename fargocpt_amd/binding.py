@@ -15,6 +15,7 @@ ABI_VERSION = 5
 OVERLAP = 7
 GEOM_PAD = 15
 MAX_BODIES = 8
+NBODY_STATE = 9
 
 # enum values (include/fargocpt_hip.h)
 SPACING_ARITHMETIC, SPACING_LOGARITHMIC, SPACING_EXPONENTIAL = 0, 1, 2
@@ -202,11 +203,78 @@ class Library:
                      s.ctypes.data_as(C.POINTER(_i32)), _i32(ns.value), C.byref(ns)), "selftest_chunk_tables")
         return t, s
 
+    def nbody(self, G: float = 1.0) -> "NBody":
+        return NBody(self, G)
+
     def comm_unique_id(self) -> bytes:
         """ncclGetUniqueId: slab 0 calls it and hands the bytes to every slab (fcpt_comm_init)."""
         buf = C.create_string_buffer(COMM_ID_BYTES)
         self.check(self.fn("comm_unique_id")(buf), "comm_unique_id")
         return buf.raw
+
+
+class NBody:
+    """fcpt_nbody_*: the point masses of the planetary system on the host (no GPU needed)."""
+
+    def __init__(self, lib: Library, G: float = 1.0):
+        self.lib = lib
+        self._h = C.c_void_p()
+        lib.check(lib.fn("nbody_create")(_f64(G), C.byref(self._h)), "nbody_create")
+
+    def close(self):
+        if self._h:
+            self.lib.fn("nbody_destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _call(self, name, *args):
+        self.lib.check(self.lib.fn("nbody_" + name)(self._h, *args), "nbody_" + name)
+
+    def __len__(self) -> int:
+        n = _i32()
+        self._call("count", C.byref(n))
+        return n.value
+
+    def add(self, mass, semi_major_axis=0.0, eccentricity=0.0, argument_of_pericenter=0.0, true_anomaly=0.0):
+        self._call("add", _f64(mass), _f64(semi_major_axis), _f64(eccentricity), _f64(argument_of_pericenter),
+                   _f64(true_anomaly))
+
+    def kick(self, ax, ay, dt: float):
+        ax, ay = (np.ascontiguousarray(v, dtype=np.float64) for v in (ax, ay))
+        assert ax.size == ay.size == len(self)
+        self._call("kick", _as_dp(ax), _as_dp(ay), _f64(dt))
+
+    def advance(self, dt: float):
+        self._call("advance", _f64(dt))
+
+    def centre_delta_v(self, n_centre: int, dt: float) -> np.ndarray:
+        out = np.zeros(2)
+        self._call("centre_delta_v", _i32(n_centre), _f64(dt), _as_dp(out))
+        return out
+
+    def shift_to_centre(self, n_centre: int = 1):
+        self._call("shift_to_centre", _i32(n_centre))
+
+    def rotate(self, angle: float):
+        self._call("rotate", _f64(angle))
+
+    @property
+    def state(self) -> np.ndarray:
+        """[n, 9]: x, y, vx, vy, mass and the four carried parts of the integrator's compensated additions."""
+        out = np.zeros((len(self), NBODY_STATE))
+        if out.size:
+            self._call("get_state", _as_dp(out))
+        return out
+
+    @state.setter
+    def state(self, a):
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, NBODY_STATE)
+        self._call("set_state", _i32(a.shape[0]), _as_dp(a))
 
 
 class Context:
@@ -339,6 +407,32 @@ class Context:
         self._call("disk_on_body_accel", _f64(x), _f64(y), _f64(r_object), _f64(smoothing_fixed),
                    _f64(cubic_smoothing_radius), out)
         return np.array(out[:], dtype=np.float64)
+
+    def disk_on_bodies_begin(self, x, y, r_object, smoothing_fixed, cubic_smoothing_radius):
+        """Queues the one-pass force on len(x) bodies and the copy of its 4n sums; does not block."""
+        a = [np.ascontiguousarray(v, dtype=np.float64) for v in (x, y, r_object, smoothing_fixed, cubic_smoothing_radius)]
+        assert all(v.shape == a[0].shape and v.ndim == 1 for v in a)
+        self._dob_n = a[0].size
+        self._call("disk_on_bodies_begin", _i32(a[0].size), *(_as_dp(v) for v in a))
+
+    def disk_on_bodies_end(self) -> np.ndarray:
+        """Waits for the pending pass: [n, 4] = {inner a_x, inner a_y, outer a_x, outer a_y} per body, this slab's."""
+        out = np.zeros((max(getattr(self, "_dob_n", 0), 1), 4))
+        self._call("disk_on_bodies_end", _as_dp(out))
+        return out
+
+    def disk_on_bodies(self, x, y, r_object, smoothing_fixed=None, cubic_smoothing_radius=None):
+        """ComputeDiskOnPlanetAccel for all bodies in one pass over the grid (begin + end)."""
+        n = len(x)
+        self.disk_on_bodies_begin(x, y, r_object, np.full(n, -1.0) if smoothing_fixed is None else smoothing_fixed,
+                                  np.zeros(n) if cubic_smoothing_radius is None else cubic_smoothing_radius)
+        return self.disk_on_bodies_end()
+
+    def allreduce_sum(self, values) -> np.ndarray:
+        """SUM over the slabs of the communicator (the same bits on every slab); without one: the input."""
+        v = np.array(values, dtype=np.float64).ravel()
+        self._call("allreduce_sum", _i32(v.size), _as_dp(v))
+        return v.reshape(np.shape(values))
 
     def cfl(self) -> float:
         v = _f64()

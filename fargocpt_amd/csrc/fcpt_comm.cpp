@@ -198,7 +198,9 @@ struct Comm {
     int rank = 0, nranks = 1;
     HostLink *host = nullptr; // the host-staged transport instead of RCCL
     double *d_scratch = nullptr; // RCCL: operand of the barrier's all-reduce
+    double *d_sum = nullptr;     // RCCL: operand of comm_allreduce_sum (kSumMax doubles)
 };
+constexpr int kSumMax = 4 * FCPT_MAX_BODIES;
 
 int comm_unique_id(void *id128)
 {
@@ -323,6 +325,8 @@ void comm_destroy(Comm *c)
         (void)g_rccl.CommDestroy(c->comm);
     if (c->d_scratch)
         (void)hipFree(c->d_scratch);
+    if (c->d_sum)
+        (void)hipFree(c->d_sum);
     link_close(c->host, c->rank == 0);
     delete c;
 }
@@ -346,6 +350,25 @@ int link_allreduce_min(Comm *c, double *value)
         m = o->v < m ? o->v : m;
     }
     *value = m;
+    return FCPT_OK;
+}
+// SUM over the ranks of one double through the same slots: every rank adds the ranks' values in rank order, so all
+// of them end with the same bits
+int link_allreduce_sum(Comm *c, double *value)
+{
+    HostLink *h = c->host;
+    const uint64_t s = ++h->rseq;
+    LinkSlot *mine = h->slot(c->rank, (int)(s & 1));
+    mine->v = *value;
+    __atomic_store_n(&mine->seq, s, __ATOMIC_RELEASE);
+    double sum = 0.0;
+    for (int r = 0; r < c->nranks; ++r) {
+        LinkSlot *o = h->slot(r, (int)(s & 1));
+        if (!link_wait(h, &o->seq, s, "SUM reduction"))
+            return FCPT_ECOMM;
+        sum = r == 0 ? o->v : sum + o->v;
+    }
+    *value = sum;
     return FCPT_OK;
 }
 int link_exchange(Comm *c, int peer_inner, const double *send_inner, double *recv_inner, int peer_outer,
@@ -460,6 +483,37 @@ int comm_allreduce_min(Comm *c, double *d_value, hipStream_t st)
         return FCPT_OK;
     }
     NCHK(g_rccl.AllReduce(d_value, d_value, 1, ncclDouble, ncclMin, c->comm, st));
+    return FCPT_OK;
+}
+
+// Force.cpp:115
+int comm_allreduce_sum(Comm *c, int n, double *values, hipStream_t st)
+{
+    if (!c || (!c->comm && !c->host) || !values || n < 0 || n > kSumMax)
+        return FCPT_EINVAL;
+    if (c->nranks == 1 || n == 0)
+        return FCPT_OK;
+    if (c->host) { // one value per round of the reduction slots: a rehearsal transport, not a fast one
+        for (int k = 0; k < n; ++k)
+            if (int rc = link_allreduce_sum(c, values + k))
+                return rc;
+        return FCPT_OK;
+    }
+    // (not executed on a one-GPU machine, like the other RCCL branches of this file)
+    if (!c->d_sum && hipMalloc((void **)&c->d_sum, kSumMax * sizeof(double)) != hipSuccess) {
+        set_error("comm_allreduce_sum: hipMalloc failed");
+        return FCPT_ENOMEM;
+    }
+    if (hipMemcpyAsync(c->d_sum, values, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess) {
+        set_error("comm_allreduce_sum: upload failed");
+        return FCPT_EHIP;
+    }
+    NCHK(g_rccl.AllReduce(c->d_sum, c->d_sum, (size_t)n, ncclDouble, ncclSum, c->comm, st));
+    if (hipMemcpyAsync(values, c->d_sum, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+        set_error("comm_allreduce_sum: download failed");
+        return FCPT_EHIP;
+    }
     return FCPT_OK;
 }
 

@@ -34,6 +34,10 @@ int comm_size(const Comm *c);
 int comm_neighbour_exchange(Comm *c, int peer_inner, const double *send_inner, double *recv_inner, int peer_outer,
                             const double *send_outer, double *recv_outer, size_t count, hipStream_t st);
 int comm_allreduce_min(Comm *c, double *d_value, hipStream_t st);
+// Force.cpp:115: SUM over the ranks of n host doubles, in place, the same bits on every rank.  Host-staged: every rank
+// adds the ranks' values in rank order.  RCCL: ncclAllReduce(ncclSum) through a device buffer of the communicator.
+// Blocks; the caller's stream is only used for the staging copies of the RCCL branch.
+int comm_allreduce_sum(Comm *c, int n, double *values, hipStream_t st);
 // MPI_Barrier (+ completion of the work queued on st)
 int comm_barrier(Comm *c, hipStream_t st);
 

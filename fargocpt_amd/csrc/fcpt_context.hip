@@ -843,6 +843,10 @@ int fcpt_destroy(fcpt_ctx *c)
         (void)hipFree(p);
     if (c->h_clk)
         (void)hipHostFree(c->h_clk);
+    if (c->dob_host)
+        (void)hipHostFree(c->dob_host);
+    if (c->e_dob)
+        (void)hipEventDestroy(c->e_dob);
     for (hipEvent_t e : c->prof.events)
         (void)hipEventDestroy(e);
     if (c->side) {
@@ -1083,6 +1087,59 @@ int fcpt_disk_on_body_accel(fcpt_ctx *c, double x, double y, double r_object, do
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d_out, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return FCPT_OK;
+}
+
+int fcpt_disk_on_bodies_begin(fcpt_ctx *c, int32_t n, const double *x, const double *y, const double *r_object,
+                              const double *smoothing_fixed, const double *cubic_smoothing_radius)
+{
+    if (!c || n < 1 || n > FCPT_MAX_BODIES || !x || !y || !r_object || !smoothing_fixed || !cubic_smoothing_radius) {
+        set_error("fcpt_disk_on_bodies_begin: null argument or n = %d outside 1 .. %d", (int)n, FCPT_MAX_BODIES);
+        return FCPT_EINVAL;
+    }
+    const size_t nblocks = disk_on_bodies_blocks(c->P);
+    if (!c->dob_part) {
+        if (int rc = dev_alloc(c, &c->dob_part, 4 * (nblocks + 1) * FCPT_MAX_BODIES))
+            return rc;
+        if (hipHostMalloc((void **)&c->dob_host, 4 * FCPT_MAX_BODIES * sizeof(double)) != hipSuccess) {
+            set_error("hipHostMalloc failed");
+            return FCPT_ENOMEM;
+        }
+        HIPCHK(hipEventCreateWithFlags(&c->e_dob, hipEventDisableTiming));
+    }
+    join_side(c);
+    ProfScope prof_scope(c);
+    DiskBodies B;
+    std::memset(&B, 0, sizeof(B));
+    bool need_h = false;
+    for (int k = 0; k < n; ++k) {
+        B.x[k] = x[k];
+        B.y[k] = y[k];
+        B.r_object[k] = r_object[k];
+        B.smoothing_fixed[k] = smoothing_fixed[k];
+        B.r_sm[k] = cubic_smoothing_radius[k];
+        need_h = need_h || smoothing_fixed[k] < 0.0;
+    }
+    if (need_h && c->P.adiabatic && !c->P.lazy_derived)
+        ensure_pressure(c); // the scale-height grid
+    double *d_out = c->dob_part + 4 * nblocks * FCPT_MAX_BODIES;
+    launch_disk_on_bodies(c->P, n, B, c->dob_part, d_out, c->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->dob_host, d_out, 4 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->e_dob, c->stream));
+    c->dob_pending = n;
+    return FCPT_OK;
+}
+
+int fcpt_disk_on_bodies_end(fcpt_ctx *c, double *out)
+{
+    if (!c || !out || c->dob_pending < 1) {
+        set_error("fcpt_disk_on_bodies_end without a pending fcpt_disk_on_bodies_begin");
+        return FCPT_EINVAL;
+    }
+    HIPCHK(hipEventSynchronize(c->e_dob));
+    std::memcpy(out, c->dob_host, 4 * (size_t)c->dob_pending * sizeof(double));
+    c->dob_pending = 0;
     return FCPT_OK;
 }
 

@@ -84,6 +84,11 @@ struct fcpt_ctx {
     hipEvent_t e_fork = nullptr, e_join = nullptr;
     bool join_pending = false;
     bool pressure_valid = false;
+    // fcpt_disk_on_bodies_begin / _end: first-stage sums [body][block][4] followed by the 4 * FCPT_MAX_BODIES results
+    // (allocated by the first call), their pinned host copy, the event behind the copy, the n of the pending call
+    double *dob_part = nullptr, *dob_host = nullptr;
+    hipEvent_t e_dob = nullptr;
+    int dob_pending = 0;
     // leapfrog: bodies at the mid-step time (simulation.cpp:359-366)
     bool has_mid = false;
     double mx[FCPT_MAX_BODIES], my[FCPT_MAX_BODIES], mm[FCPT_MAX_BODIES], mrsm[FCPT_MAX_BODIES];

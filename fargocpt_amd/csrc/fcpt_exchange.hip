@@ -168,6 +168,18 @@ int fcpt_comm_barrier(fcpt_ctx *c)
     return rc == FCPT_EHIP ? FCPT_ECOMM : rc;
 }
 
+int fcpt_allreduce_sum(fcpt_ctx *c, int32_t n, double *values)
+{
+    if (!c || n < 0 || n > 4 * FCPT_MAX_BODIES || (n > 0 && !values)) {
+        set_error("fcpt_allreduce_sum: null argument or n = %d outside 0 .. %d", (int)n, 4 * FCPT_MAX_BODIES);
+        return FCPT_EINVAL;
+    }
+    if (!c->comm)
+        return FCPT_OK; // a single slab: its sums are the sums
+    const int rc = comm_allreduce_sum(c->comm, n, values, c->stream);
+    return rc == FCPT_EHIP ? FCPT_ECOMM : rc;
+}
+
 int fcpt_comm_destroy(fcpt_ctx *c)
 {
     if (!c)

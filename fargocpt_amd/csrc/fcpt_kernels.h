@@ -21,7 +21,8 @@ enum KernelId {
     KID_SRC_FUSED, KID_AV_FUSED, KID_VISC_FUSED, KID_SOURCE_MARCH, KID_THETA_MARCH,
     KID_TRANSPORT_FUSED, KID_MASSFLOW, KID_CFL_RINGS, KID_THETA_GATED_BOUNDARY, KID_EXCHANGE_COPY,
     KID_DISK_ON_BODY, KID_VISC_FACTORS, KID_SOURCE_MARCH_ADI, KID_SOURCE_MARCH_ADI_WIDE,
-    KID_ACCEL_ON_GAS, KID_SOURCE_MARCH_ADI_ACC, KID_TRANSPORT_RADIAL_MEANS, KID_CFL_RINGS_BC, KID_COUNT
+    KID_ACCEL_ON_GAS, KID_SOURCE_MARCH_ADI_ACC, KID_TRANSPORT_RADIAL_MEANS, KID_CFL_RINGS_BC,
+    KID_DISK_ON_BODIES, KID_COUNT
 };
 static_assert(KID_COUNT <= 64, "fcpt_profile_start selects kernels with a 64-bit mask");
 extern const char *const kKernelNames[KID_COUNT];
@@ -83,6 +84,12 @@ void launch_massflow(const Dev &P, hipStream_t st);
 void launch_substep3_cooling_only(const Dev &P, hipStream_t st);
 void launch_disk_on_body(const Dev &P, double x, double y, double r_object, double smoothing_fixed, double r_sm, double *out,
                          hipStream_t st);
+// the objects of k_disk_on_bodies, by value in the kernel's arguments (entries past n are not read)
+struct DiskBodies {
+    double x[FCPT_MAX_BODIES], y[FCPT_MAX_BODIES], r_object[FCPT_MAX_BODIES], smoothing_fixed[FCPT_MAX_BODIES], r_sm[FCPT_MAX_BODIES];
+};
+size_t disk_on_bodies_blocks(const Dev &P); // blocks of the first stage: `part` holds 4 * n * blocks doubles, `out` 4 * n
+void launch_disk_on_bodies(const Dev &P, int n, const DiskBodies &B, double *part, double *out, hipStream_t st);
 void launch_source_fused(const Dev &P, hipStream_t st);
 int launch_source_march(const Dev &P, hipStream_t st, bool fold_bc, bool *bc_folded, bool fold_cfl = false);
 bool source_march_applies(const Dev &P);

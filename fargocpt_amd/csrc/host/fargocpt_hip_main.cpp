@@ -457,6 +457,7 @@ void config_to_desc(const Config &c, fcpt_desc &d)
 struct Body {
     double a, m, phase, rsm_factor;
     double rampup; // "ramp-up time" in orbital periods (planet.cpp:166-179)
+    double ecc = 0.0, pericenter = 0.0, true_anomaly = 0.0; // --bodies free (planetary_system.cpp:172-189)
 };
 
 void mkdirs(const std::string &p)
@@ -660,7 +661,7 @@ int main(int argc, char **argv)
     bool quiet = false, lenient = false;
     long max_steps = -1, restart_from = -1;
     int want_ranks = 1;
-    std::string mode, cfgpath, transport = "auto";
+    std::string mode, cfgpath, transport = "auto", bodies_mode = "circular";
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "-q")
@@ -671,6 +672,8 @@ int main(int argc, char **argv)
             want_ranks = atoi(argv[++i]);
         else if (a == "--transport" && i + 1 < argc)
             transport = lower(argv[++i]);
+        else if (a == "--bodies" && i + 1 < argc)
+            bodies_mode = lower(argv[++i]);
         else if (a == "-N" && i + 1 < argc)
             max_steps = atol(argv[++i]);
         else if (mode.empty())
@@ -682,9 +685,10 @@ int main(int argc, char **argv)
     }
     // start_mode.cpp:29-113: start | restart [N] | auto
     if ((mode != "start" && mode != "restart" && mode != "auto") || cfgpath.empty() || want_ranks < 1 ||
-        (transport != "auto" && transport != "rccl" && transport != "host")) {
+        (transport != "auto" && transport != "rccl" && transport != "host") ||
+        (bodies_mode != "circular" && bodies_mode != "free")) {
         fprintf(stderr, "usage: fargocpt_hip [-q] [--lenient] [-N steps] [--ranks n] [--transport auto|rccl|host] "
-                        "start|auto|restart [N] <config.yml>\n");
+                        "[--bodies circular|free] start|auto|restart [N] <config.yml>\n");
         return 2;
     }
     // this process's rank: FCPT_RANK / FCPT_NRANKS from the --ranks parent below or from a launcher of the caller's
@@ -736,6 +740,26 @@ int main(int argc, char **argv)
                 return 2;
             }
     }
+    // --bodies free: the bodies move under their own gravity (fcpt_nbody_*) and, with DiskFeedback, under the disk's;
+    // what that mode does not cover is refused here, before any device is asked for
+    const bool free_bodies = bodies_mode == "free";
+    const bool disk_feedback = cfg.flag("DiskFeedback", true); // parameters.cpp:788
+    if (free_bodies && d.integrator != FCPT_INTEGRATOR_EULER) {
+        fprintf(stderr, "fargocpt_hip: --bodies free needs Integrator: Euler (the drift-kick-drift of the bodies in "
+                        "step_LeapFrog is not implemented)\n");
+        return 2;
+    }
+    if (free_bodies && lower(cfg.str("HydroFrameCenter", "primary")) != "primary") {
+        fprintf(stderr, "fargocpt_hip: --bodies free needs HydroFrameCenter: primary\n");
+        return 2;
+    }
+    if (free_bodies && cfg.nbody.size() > FCPT_MAX_BODIES) {
+        fprintf(stderr, "fargocpt_hip: --bodies free: more than %d bodies\n", FCPT_MAX_BODIES);
+        return 2;
+    }
+    if (!free_bodies && cfg.has("DiskFeedback") && disk_feedback && !quiet)
+        fprintf(stderr, "fargocpt_hip: note: DiskFeedback: yes is not applied with --bodies circular (the bodies keep "
+                        "their circular orbits); --bodies free applies it\n");
     if (want_ranks > 1 && !(env_rank && env_nranks))
         return launch_ranks(want_ranks, outdir, quiet); // the n ranks run, this process only waits for them
     // start_mode::configure_start_mode (src/start_mode.cpp:29-113): auto = restart from the last snapshot of
@@ -775,10 +799,13 @@ int main(int argc, char **argv)
         o.phase = 0.0;
         o.rsm_factor = b.count("cubic smoothing factor") ? number(b.at("cubic smoothing factor"), K_NONE) : 0.0;
         o.rampup = b.count("ramp-up time") ? number(b.at("ramp-up time"), K_NONE) : 0.0;
+        o.ecc = b.count("eccentricity") ? number(b.at("eccentricity"), K_NONE) : 0.0;
+        o.pericenter = b.count("argument of pericenter") ? number(b.at("argument of pericenter"), K_NONE) : 0.0;
+        o.true_anomaly = b.count("trueanomaly") ? number(b.at("trueanomaly"), K_NONE) : 0.0;
         bodies.push_back(o);
     }
     if (bodies.empty())
-        bodies.push_back({0.0, d.hydro_center_mass, 0.0, 0.0, 0.0});
+        bodies.push_back(Body{0.0, d.hydro_center_mass, 0.0, 0.0, 0.0});
 
     std::vector<double> radii(d.nr_global + FCPT_GEOM_PAD + 1);
     CHECK(fcpt_radii(&d, radii.data()));
@@ -923,7 +950,154 @@ int main(int argc, char **argv)
         }
         CHECK(fcpt_set_bodies(ctx, n, x, y, m, rsm, itx, ity));
     };
-    set_bodies(0.0, 0.0);
+    // ---- --bodies free: the bodies as a system of their own (fcpt_nbody_*), every rank its own bit-identical copy --------
+    fcpt_nbody *nb = nullptr;
+    const int nfree = (int)bodies.size();
+    // since the last monitor row: sum of m (x a_y - y a_x) dt of the disk's force on the body, and of the disk's indirect
+    // term (minus its force on the star), as t_planet accumulates them (frame_of_reference.cpp:95-108)
+    std::vector<double> torque_acc(bodies.size(), 0.0), indirect_acc(bodies.size(), 0.0);
+    double bstate[FCPT_MAX_BODIES * FCPT_NBODY_STATE];
+    if (free_bodies) {
+        CHECK(fcpt_nbody_create(d.G, &nb));
+        for (const Body &b : bodies)
+            CHECK(fcpt_nbody_add(nb, b.m, b.a, b.ecc, b.pericenter, b.true_anomaly));
+        CHECK(fcpt_nbody_shift_to_centre(nb, 1)); // HydroFrameCenter: primary
+    }
+    const bool no_star_smoothing = cfg.flag("CompatibilityNoStarSmoothing", false);
+    const bool smoothing_planetloc = cfg.flag("CompatibilitySmoothingPlanetLoc", false);
+    // arguments of the disk's force on every body at the current positions (compute_smoothing, Force.cpp:145-159)
+    auto queue_disk_force = [&]() {
+        double x[FCPT_MAX_BODIES], y[FCPT_MAX_BODIES], r[FCPT_MAX_BODIES], sm[FCPT_MAX_BODIES], rsm[FCPT_MAX_BODIES];
+        CHECK(fcpt_nbody_get_state(nb, bstate));
+        for (int k = 0; k < nfree; ++k) {
+            const double *q = bstate + FCPT_NBODY_STATE * k;
+            x[k] = q[0];
+            y[k] = q[1];
+            r[k] = std::sqrt(q[0] * q[0] + q[1] * q[1]);
+            sm[k] = -1.0; // ThicknessSmoothing x H of each cell
+            if (no_star_smoothing && k == 0)
+                sm[k] = 0.0;
+            else if (smoothing_planetloc)
+                sm[k] = d.thickness_smoothing * d.aspect_ratio * std::pow(r[k], 1.0 + d.flaring_index);
+            rsm[k] = bodies[k].a * std::cbrt(bodies[k].m / (3.0 * d.hydro_center_mass)) * bodies[k].rsm_factor;
+        }
+        CHECK(fcpt_disk_on_bodies_begin(ctx, nfree, x, y, r, sm, rsm));
+    };
+    // inner + outer sums of all slabs: the disk's specific force on body k in (ax[k], ay[k])
+    auto collect_disk_force = [&](double *ax, double *ay) {
+        double f[4 * FCPT_MAX_BODIES];
+        CHECK(fcpt_disk_on_bodies_end(ctx, f));
+        if (slab.multi())
+            CHECK(fcpt_allreduce_sum(ctx, 4 * nfree, f));
+        for (int k = 0; k < nfree; ++k) {
+            ax[k] = f[4 * k] + f[4 * k + 2];
+            ay[k] = f[4 * k + 1] + f[4 * k + 3];
+        }
+    };
+    // step_Euler up to the potential (simulation.cpp:155-175) for a step of length dt from the force (ax, ay) on the state
+    // at its start: disk kick, both indirect terms, bodies to the context, indirect term on the bodies.  dt = 0: only the
+    // bodies go to the context.
+    auto set_bodies_free = [&](double t, double dt, const double *ax, const double *ay) {
+        double itx = 0.0, ity = 0.0;
+        if (dt > 0.0 && disk_feedback) {
+            CHECK(fcpt_nbody_get_state(nb, bstate));
+            for (int k = 0; k < nfree; ++k) {
+                const double *q = bstate + FCPT_NBODY_STATE * k;
+                torque_acc[k] += q[4] * (q[0] * ay[k] - q[1] * ax[k]) * dt;
+                indirect_acc[k] += q[4] * (q[1] * ax[0] - q[0] * ay[0]) * dt;
+            }
+            CHECK(fcpt_nbody_kick(nb, ax, ay, dt)); // UpdatePlanetVelocitiesWithDiskForce
+            itx -= ax[0];                            // ComputeIndirectTermDisk: one centre body
+            ity -= ay[0];
+        }
+        if (dt > 0.0 && nfree > 1) { // ComputeIndirectTermNbody, IndirectTermMode 0
+            double dv[2];
+            CHECK(fcpt_nbody_centre_delta_v(nb, 1, dt, dv));
+            itx -= dv[0] / dt;
+            ity -= dv[1] / dt;
+        }
+        double x[FCPT_MAX_BODIES], y[FCPT_MAX_BODIES], m[FCPT_MAX_BODIES], rsm[FCPT_MAX_BODIES];
+        CHECK(fcpt_nbody_get_state(nb, bstate));
+        for (int k = 0; k < nfree; ++k) {
+            const Body &b = bodies[k];
+            const double *q = bstate + FCPT_NBODY_STATE * k;
+            x[k] = q[0];
+            y[k] = q[1];
+            m[k] = q[4];
+            const double om = b.a > 0 ? std::sqrt(d.G * (d.hydro_center_mass + b.m) / (b.a * b.a * b.a)) : 0.0;
+            if (b.rampup > 0 && om > 0) {
+                const double period = 2 * M_PI / om;
+                if (t < b.rampup * period) {
+                    const double cs = std::cos(t * M_PI_2 / (b.rampup * period));
+                    m[k] = b.m * (1.0 - cs * cs);
+                }
+            }
+            rsm[k] = b.a * std::cbrt(b.m / (3.0 * d.hydro_center_mass)) * b.rsm_factor;
+        }
+        CHECK(fcpt_set_bodies(ctx, nfree, x, y, m, rsm, itx, ity));
+        if (dt > 0.0) { // apply_indirect_term_on_Nbody
+            double kx[FCPT_MAX_BODIES], ky[FCPT_MAX_BODIES];
+            for (int k = 0; k < nfree; ++k) {
+                kx[k] = itx;
+                ky[k] = ity;
+            }
+            CHECK(fcpt_nbody_kick(nb, kx, ky, dt));
+        }
+    };
+    // the rest of the step for the bodies (simulation.cpp:222-224) and the frame's rotation
+    auto advance_bodies = [&](double dt) {
+        CHECK(fcpt_nbody_advance(nb, dt));
+        CHECK(fcpt_nbody_shift_to_centre(nb, 1));
+        if (d.omega_frame != 0.0)
+            CHECK(fcpt_nbody_rotate(nb, -d.omega_frame * dt));
+    };
+    // monitor/nbody<k>.dat (t_planet::write, nbody/planet.cpp:283-374): the reference's columns; those this driver has no
+    // source for (circumplanetary mass, anomalies, accretion) are written as 0
+    auto write_nbody_rows = [&](unsigned nsnap, unsigned nmon, double t, bool create) {
+        if (!slab.master())
+            return;
+        CHECK(fcpt_nbody_get_state(nb, bstate));
+        for (int k = 0; k < nfree; ++k) {
+            const std::string fn = outdir + "monitor/nbody" + std::to_string(k) + ".dat";
+            FILE *f = fopen(fn.c_str(), create ? "w" : "a");
+            if (!f) {
+                fprintf(stderr, "fargocpt_hip: cannot write %s\n", fn.c_str());
+                exit(1);
+            }
+            if (create) {
+                const char *cols[] = {"snapshot number | 1", "monitor number | 1", "x | length", "y | length", "vx | velocity",
+                                      "vy | velocity", "mass | mass", "time | time", "omega frame | frequency",
+                                      "mdcp | mass", "eccentricity | 1", "angular momentum | angular momentum",
+                                      "semi-major axis | length", "omega kepler | frequency", "mean anomaly | 1",
+                                      "eccentric anomaly | 1", "true anomaly | 1", "pericenter angle | 1", "torque | torque",
+                                      "accreted torque | torque", "indirect torque | torque", "accretion rate | mass accretion rate"};
+                fprintf(f, "#FargoCPT planet file for planet: %d\n#version: 2\n", k);
+                for (int c = 0; c < 22; ++c)
+                    fprintf(f, "#variable: %d | %s\n", c, cols[c]);
+            }
+            const double *q = bstate + FCPT_NBODY_STATE * k, *q0 = bstate;
+            double ecc = 0.0, sma = 0.0, omk = 0.0;
+            const double rx = q[0] - q0[0], ry = q[1] - q0[1], vx = q[2] - q0[2], vy = q[3] - q0[3];
+            const double h = rx * vy - ry * vx, mu = d.G * (q0[4] + q[4]), r = std::sqrt(rx * rx + ry * ry);
+            if (k > 0 && r > 0.0 && mu > 0.0) {
+                sma = 1.0 / (2.0 / r - (vx * vx + vy * vy) / mu);
+                const double e2 = 1.0 - h * h / (mu * sma);
+                ecc = e2 > 0.0 ? std::sqrt(e2) : 0.0;
+                omk = sma > 0.0 ? std::sqrt(mu / (sma * sma * sma)) : 0.0;
+            }
+            fprintf(f, "%u\t%u\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g"
+                       "\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\t%#.18g\n",
+                    nsnap, nmon, q[0], q[1], q[2], q[3], q[4], t, d.omega_frame, 0.0, ecc, q[4] * (q[0] * q[3] - q[1] * q[2]), sma,
+                    omk, 0.0, 0.0, 0.0, 0.0, torque_acc[k] / d.monitor_timestep, 0.0, indirect_acc[k] / d.monitor_timestep, 0.0);
+            fclose(f);
+        }
+        std::fill(torque_acc.begin(), torque_acc.end(), 0.0);
+        std::fill(indirect_acc.begin(), indirect_acc.end(), 0.0);
+    };
+    if (free_bodies)
+        set_bodies_free(0.0, 0.0, nullptr, nullptr);
+    else
+        set_bodies(0.0, 0.0);
     { // irradiating bodies: 'temperature', 'radius', 'irradiation ramp-up time' (planetary_system.cpp:160-250)
         double temp[FCPT_MAX_BODIES] = {0}, rad[FCPT_MAX_BODIES] = {0}, ramp[FCPT_MAX_BODIES] = {0};
         bool any = false;
@@ -1084,6 +1258,17 @@ int main(int argc, char **argv)
         barrier(); // the grids are complete before misc.bin and list.txt announce the snapshot
         if (!slab.master())
             return;
+        if (free_bodies) { // nbody.bin: uint32 version (1), uint32 n, n x FCPT_NBODY_STATE doubles (fcpt_nbody_get_state)
+            const uint32_t head[2] = {1u, (uint32_t)nfree};
+            CHECK(fcpt_nbody_get_state(nb, bstate));
+            FILE *bf = fopen((dir + "nbody.bin").c_str(), "wb");
+            if (!bf || fwrite(head, sizeof(head), 1, bf) != 1 ||
+                fwrite(bstate, sizeof(double), (size_t)nfree * FCPT_NBODY_STATE, bf) != (size_t)nfree * FCPT_NBODY_STATE) {
+                fprintf(stderr, "fargocpt_hip: cannot write %snbody.bin\n", dir.c_str());
+                exit(1);
+            }
+            fclose(bf);
+        }
         misc_entry misc;
         memset(&misc, 0, sizeof(misc));
         misc.timestep = nsnap;
@@ -1173,11 +1358,43 @@ int main(int argc, char **argv)
         time = misc.time;
         n_monitor = misc.nTimeStep;
         n_iter = n_iter_last = misc.N_iter;
-        set_bodies(time, 0.0);
+        if (free_bodies) {
+            uint32_t head[2] = {0, 0};
+            FILE *bf = fopen((restart_dir + "nbody.bin").c_str(), "rb");
+            if (!bf || fread(head, sizeof(head), 1, bf) != 1 || head[0] != 1u || head[1] != (uint32_t)nfree ||
+                fread(bstate, sizeof(double), (size_t)nfree * FCPT_NBODY_STATE, bf) != (size_t)nfree * FCPT_NBODY_STATE) {
+                fprintf(stderr, "fargocpt_hip: cannot read the state of %d bodies from %snbody.bin (written by --bodies free)\n",
+                        nfree, restart_dir.c_str());
+                return 1;
+            }
+            fclose(bf);
+            CHECK(fcpt_nbody_set_state(nb, nfree, bstate));
+            set_bodies_free(time, 0.0, nullptr, nullptr);
+        } else {
+            set_bodies(time, 0.0);
+        }
         CHECK(fcpt_recalculate_derived(ctx));
         if (!quiet)
             printf("Restarting from %s at time %f (snapshot %u, monitor step %u).\n", restart_dir.c_str(), time,
                    misc.timestep, misc.nTimeStep);
+    }
+    if (free_bodies && !restarting) {
+        if (disk_feedback) { // correct_velocity_for_disk_accel (main.cpp:123-126, planetary_system.cpp:895-939)
+            double ax[FCPT_MAX_BODIES], ay[FCPT_MAX_BODIES];
+            queue_disk_force();
+            collect_disk_force(ax, ay);
+            CHECK(fcpt_nbody_get_state(nb, bstate));
+            for (int k = 0; k < nfree; ++k) {
+                double *q = bstate + FCPT_NBODY_STATE * k;
+                const double v2 = q[2] * q[2] + q[3] * q[3], ar = ax[k] * q[0] + ay[k] * q[1]; // v_new^2 / r = v_old^2 / r - a_r
+                if (v2 == 0.0 || ar > v2)
+                    continue;
+                const double scale = std::sqrt(v2 - ar) / std::sqrt(v2);
+                q[2] *= scale;
+                q[3] *= scale;
+            }
+            CHECK(fcpt_nbody_set_state(nb, nfree, bstate));
+        }
     }
     exchange(); // CommunicateBoundariesAll, main.cpp:147
     if (!restarting)
@@ -1198,7 +1415,10 @@ int main(int argc, char **argv)
     double sum_dt = 0, min_dt = 1e300, max_dt = 0;
     const auto t_start = std::chrono::steady_clock::now();
     auto t_last = t_start;
-    const bool moving = bodies.size() > 1;
+    const bool moving = bodies.size() > 1 || free_bodies;
+    if (free_bodies && !restarting) {
+        write_nbody_rows(0, 0, 0.0, true);
+    }
     // Between two monitor times the loop of sim::run does nothing but step: as long as the monitor-time snapping
     // cannot trigger (simulation.cpp:528-540: it needs time_left < 1.05 dt, and dt grows by at most CFLmaxVar per
     // step) those steps are exactly the ones fcpt_run_steps takes with dt resident on the device -- no read-back of
@@ -1239,14 +1459,23 @@ int main(int argc, char **argv)
                 continue;
             }
         }
+        if (free_bodies)
+            queue_disk_force(); // on the state at the start of the step; the wait of the CFL value covers it
         const double cfl_dt = calc_dt();
         last_dt = cfl_dt;
         double step_dt;
         CHECK(fcpt_snap_to_monitor(ctx, cfl_dt, &step_dt));
         const double time_next_monitor = (n_monitor + 1) * d.monitor_timestep;
-        if (moving)
+        if (free_bodies) {
+            double ax[FCPT_MAX_BODIES], ay[FCPT_MAX_BODIES];
+            collect_disk_force(ax, ay);
+            set_bodies_free(time, step_dt, ax, ay);
+        } else if (moving) {
             set_bodies(time, step_dt);
+        }
         CHECK(fcpt_step(ctx, step_dt));
+        if (free_bodies)
+            advance_bodies(step_dt); // on the host, under the step's kernels
         exchange(); // simulation.cpp:236
         CHECK(fcpt_post(ctx, step_dt));
         time += step_dt;
@@ -1274,6 +1503,8 @@ int main(int argc, char **argv)
             sum_dt = 0;
             min_dt = 1e300;
             max_dt = 0;
+            if (free_bodies)
+                write_nbody_rows(clk.n_snapshot, n_monitor, time, false);
             if (n_monitor % (unsigned)d.nmonitor == 0) // handle_outputs, simulation.cpp:50-66
                 write_snapshot(n_monitor / (unsigned)d.nmonitor, n_monitor);
         }
@@ -1287,5 +1518,6 @@ int main(int argc, char **argv)
         printf("-- Final: Total Hydrosteps %lu, Time %.2f, Walltime %.2f seconds, Time per Step: %.2f milliseconds\n", n_iter,
                time, wall, n_iter ? 1e3 * wall / n_iter : 0.0);
     fcpt_destroy(ctx);
+    fcpt_nbody_destroy(nb);
     return 0;
 }

@@ -81,6 +81,112 @@ __global__ void __launch_bounds__(256) k_disk_on_body_final(const double *part, 
         out[threadIdx.x] = (s_a[0][threadIdx.x] + s_a[1][threadIdx.x]) + (s_a[2][threadIdx.x] + s_a[3][threadIdx.x]);
 }
 
+// The same sums for NBODY objects from one pass over the grid: the cell's Sigma (and the H of cell-wise smoothing,
+// obtained as above) is loaded once and serves every body; the bodies' parameters are kernel arguments (wave-uniform:
+// scalar registers), the 4 * NBODY accumulators stay in vector registers (NBODY is a template argument, the body loop
+// is unrolled).  Thread-to-cell map, the order of a thread's rings, the shuffle tree, the block fold and the final
+// stage are those of k_disk_on_body, body by body, and so is the operand order of a cell's arithmetic: body k's four
+// sums are the bits of the single-body call.  part[body][block][4]; k_disk_on_bodies_final: one block per body.
+// A copy of v the compiler cannot trace back to v (an empty asm statement: no instruction).  Each body's arithmetic
+// starts from such copies of the cell's values, so that no sub-expression (r cos(phi), smooth^2) is shared between
+// bodies: a shared product could not be contracted into the fused multiply-adds that k_disk_on_body's one body gets,
+// and the two kernels' last bits would part.
+__device__ __forceinline__ double dob_private(double v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
+template <int NBODY>
+__global__ void __launch_bounds__(256) k_disk_on_bodies(const Dev P, const DiskBodies B, int need_h, double *part)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int r0 = P.first_active + blockIdx.y * DOB_ROWS;
+    const int r1 = r0 + DOB_ROWS < P.active_size ? r0 + DOB_ROWS : P.active_size;
+    double a[NBODY][4];
+#pragma unroll
+    for (int b = 0; b < NBODY; ++b)
+        a[b][0] = a[b][1] = a[b][2] = a[b][3] = 0.0;
+    if (j < P.nphi) {
+        const double cj = P.cosphi[j], sj = P.sinphi[j];
+        for (int i = r0; i < r1; ++i) {
+            const double rm = P.Rmed[i];
+            const double sig = P.sigma[IDX(i, j)];
+            double smooth_h = 0.0;
+            if (need_h) { // compute_smoothing_scaleheight (Force.cpp:124-131), once per cell
+                double H;
+                if (!P.adiabatic) {
+                    H = P.cs_ring[i] * P.g_inv_omk[i];
+                } else if (P.lazy_derived) {
+                    const double cs = sqrt(P.gamma * (P.gamma - 1.0) * P.energy[IDX(i, j)] / sig);
+                    H = cs / (sqrt(P.gamma)) * P.g_inv_omk[i];
+                } else {
+                    H = P.scale_height[IDX(i, j)];
+                }
+                smooth_h = P.thickness_smoothing * H;
+            }
+            const double cellmass = P.Surf[i] * sig;
+#pragma unroll
+            for (int b = 0; b < NBODY; ++b) {
+                const double smooth = dob_private(B.smoothing_fixed[b] < 0.0 ? smooth_h : B.smoothing_fixed[b]);
+                const double r_sm = B.r_sm[b];
+                const double rm_b = dob_private(rm);
+                const double dx = rm_b * dob_private(cj) - B.x[b];
+                const double dy = rm_b * dob_private(sj) - B.y[b];
+                const double dist_sm_2 = dx * dx + dy * dy + smooth * smooth;
+                const double dist_sm = sqrt(dist_sm_2);
+                const double inv_dist_sm_3 = 1.0 / (dist_sm_2 * dist_sm);
+                double klahr = 1.0;
+                if (r_sm > 0.0 && dist_sm < r_sm) {
+                    const double q = dist_sm / r_sm;
+                    klahr = -(3.0 * ((q * q) * (q * q)) - 4.0 * (q * q * q));
+                }
+                const double fx = P.G * cellmass * dx * inv_dist_sm_3 * klahr;
+                const double fy = P.G * cellmass * dy * inv_dist_sm_3 * klahr;
+                const int o = rm < B.r_object[b] ? 0 : 2; // (a whole ring is inside or outside)
+                a[b][o] += fx;
+                a[b][o + 1] += fy;
+            }
+        }
+    }
+    __shared__ double s_a[NBODY][4][4];
+#pragma unroll
+    for (int b = 0; b < NBODY; ++b)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            double v = a[b][q];
+            for (int off = 32; off > 0; off >>= 1)
+                v += __shfl_down(v, off, 64);
+            if ((threadIdx.x & 63) == 0)
+                s_a[b][threadIdx.x >> 6][q] = v;
+        }
+    __syncthreads();
+    if (threadIdx.x < 4 * NBODY) {
+        const int b = threadIdx.x >> 2, q = threadIdx.x & 3;
+        const size_t nblocks = (size_t)gridDim.x * gridDim.y;
+        part[(b * nblocks + (blockIdx.y * gridDim.x + blockIdx.x)) * 4 + q] =
+            (s_a[b][0][q] + s_a[b][1][q]) + (s_a[b][2][q] + s_a[b][3][q]);
+    }
+}
+__global__ void __launch_bounds__(256) k_disk_on_bodies_final(const double *part_all, int nblocks, double *out_all)
+{
+    const double *part = part_all + (size_t)blockIdx.x * nblocks * 4;
+    double *out = out_all + 4 * blockIdx.x;
+    __shared__ double s_a[4][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        double v = 0.0;
+        for (int n = threadIdx.x; n < nblocks; n += blockDim.x)
+            v += part[n * 4 + q];
+        for (int off = 32; off > 0; off >>= 1)
+            v += __shfl_down(v, off, 64);
+        if ((threadIdx.x & 63) == 0)
+            s_a[threadIdx.x >> 6][q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        out[threadIdx.x] = (s_a[0][threadIdx.x] + s_a[1][threadIdx.x]) + (s_a[2][threadIdx.x] + s_a[3][threadIdx.x]);
+}
+
 // ---------------------------------------------------------------------------
 // boundary_conditions/{zero_gradient,reference,reflecting,outflow,keplerian_*,zero_shear}.cpp
 // called in the order of boundary_conditions.cpp:65-114; one thread per phi column.

@@ -13,7 +13,7 @@ const char *const kKernelNames[KID_COUNT] = {
     "k_transport_theta_march", "k_transport_fused", "k_massflow", "k_cfl_rings", "k_theta_march_gated_boundary",
     "k_exchange_copy", "k_disk_on_body", "k_visc_factors", "k_source_march_adi", "k_source_march_adi_wide",
     "k_accel_on_gas", "k_source_march_adi_acc",
-    "k_transport_radial_means", "k_cfl_rings_bc"};
+    "k_transport_radial_means", "k_cfl_rings_bc", "k_disk_on_bodies"};
 
 thread_local Profiler *g_prof = nullptr;
 
@@ -956,6 +956,36 @@ void launch_disk_on_body(const Dev &P, double x, double y, double r_object, doub
     const dim3 grid((P.nphi + 255) / 256, nrows > 0 ? (nrows + DOB_ROWS - 1) / DOB_ROWS : 1), block(256);
     KLAUNCH(KID_DISK_ON_BODY, k_disk_on_body, grid, block, P, x, y, r_object, smoothing_fixed, r_sm, P.cfl_part);
     KLAUNCH(KID_DISK_ON_BODY, k_disk_on_body_final, dim3(1), dim3(256), (const double *)P.cfl_part, (int)(grid.x * grid.y), out);
+}
+
+static dim3 disk_on_body_grid(const Dev &P)
+{
+    const int nrows = P.active_size - P.first_active;
+    return dim3((P.nphi + 255) / 256, nrows > 0 ? (nrows + DOB_ROWS - 1) / DOB_ROWS : 1);
+}
+size_t disk_on_bodies_blocks(const Dev &P)
+{
+    const dim3 grid = disk_on_body_grid(P);
+    return (size_t)grid.x * grid.y;
+}
+void launch_disk_on_bodies(const Dev &P, int n, const DiskBodies &B, double *part, double *out, hipStream_t st)
+{
+    const dim3 grid = disk_on_body_grid(P), block(256); // the grid of launch_disk_on_body: the same reduction tree
+    int need_h = 0;
+    for (int b = 0; b < n; ++b)
+        need_h |= B.smoothing_fixed[b] < 0.0;
+#define DOB_CASE(N_)                                                                                        \
+    case N_:                                                                                                \
+        KLAUNCH(KID_DISK_ON_BODIES, k_disk_on_bodies<N_>, grid, block, P, B, need_h, part);                 \
+        break;
+    switch (n) {
+        DOB_CASE(1) DOB_CASE(2) DOB_CASE(3) DOB_CASE(4) DOB_CASE(5) DOB_CASE(6) DOB_CASE(7) DOB_CASE(8)
+    default:
+        return;
+    }
+#undef DOB_CASE
+    static_assert(FCPT_MAX_BODIES == 8, "one instance of k_disk_on_bodies per body count");
+    KLAUNCH(KID_DISK_ON_BODIES, k_disk_on_bodies_final, dim3(n), dim3(256), (const double *)part, (int)(grid.x * grid.y), out);
 }
 
 // rings whose CFL terms read nothing the ghost exchange or the boundary kernels write: ring i reads rows i

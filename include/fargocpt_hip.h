@@ -286,6 +286,42 @@ int fcpt_initial_fields(fcpt_desc *d, const double *radii, double *sigma, double
 
 const char *fcpt_last_error(void);
 
+/* ---- the bodies as a system of their own (no GPU needed) ------------------
+ * t_planetary_system (src/nbody/planetary_system.cpp) reduced to what the gas path's driver needs: up to
+ * FCPT_MAX_BODIES point masses in the plane with positions and velocities, advanced under their mutual Newtonian
+ * gravity by an extrapolation integrator (modified midpoint rule, sub-step counts 2 .. 16, Aitken-Neville in h^2:
+ * order 16; internal sub-steps bounded by a tenth of the shortest two-body time and halved until the last column
+ * is at rounding level).  Deterministic: the same state and arguments give the same bits on every rank.
+ * Accuracy: the reference's circ_kepler_orbit criterion (1e-11 in position over 20 orbits in 2000 steps). */
+typedef struct fcpt_nbody fcpt_nbody;
+int fcpt_nbody_create(double G, fcpt_nbody **out);
+int fcpt_nbody_destroy(fcpt_nbody *s);
+int fcpt_nbody_count(const fcpt_nbody *s, int32_t *n);
+/* init_planet's placement (planetary_system.cpp:162-217,483-575): the first body rests at the origin; the second is
+ * put on the orbit with these elements about the first and both are moved about their barycentre (the heavier one
+ * nearest the origin); every further body's elements are Jacobi elements about the centre of mass of the bodies
+ * already there.  Angles in radians; a body with semi_major_axis 0 sits at that centre at rest. */
+int fcpt_nbody_add(fcpt_nbody *s, double mass, double semi_major_axis, double eccentricity, double argument_of_pericenter,
+                   double true_anomaly);
+/* v += a dt with one acceleration per body (UpdatePlanetVelocitiesWithDiskForce, src/Pframeforce.cpp:275-293;
+ * apply_indirect_term_on_Nbody) */
+int fcpt_nbody_kick(fcpt_nbody *s, const double *ax, const double *ay, double dt);
+/* integrate over dt (t_planetary_system::integrate); dt < 0 integrates backwards */
+int fcpt_nbody_advance(fcpt_nbody *s, double dt);
+/* Velocity change of the centre of mass of the first n_centre bodies over a trial advance of dt that leaves the
+ * system unchanged: what ComputeIndirectTermNbody (src/frame_of_reference.cpp:135-165) divides by dt. */
+int fcpt_nbody_centre_delta_v(const fcpt_nbody *s, int32_t n_centre, double dt, double out[2]);
+/* positions and velocities relative to the centre of mass of the first n_centre bodies (move_to_hydro_frame_center) */
+int fcpt_nbody_shift_to_centre(fcpt_nbody *s, int32_t n_centre);
+/* rotate positions and velocities by `angle` about the origin (the frame's rotation: angle = -OmegaFrame dt) */
+int fcpt_nbody_rotate(fcpt_nbody *s, double angle);
+/* The full state (restart files), FCPT_NBODY_STATE doubles per body: {x, y, vx, vy, mass} and the four parts that the
+ * integrator's compensated additions carry from step to step (0 for a body set from outside); with them a restored
+ * system continues bit for bit.  get fills FCPT_NBODY_STATE * count doubles. */
+#define FCPT_NBODY_STATE 9
+int fcpt_nbody_get_state(const fcpt_nbody *s, double *state);
+int fcpt_nbody_set_state(fcpt_nbody *s, int32_t n, const double *state);
+
 /* ---- context ------------------------------------------------------------ */
 
 /* One process per GPU (the reference: one MPI rank per slab, src/parallel.cpp:28-40): the number of HIP devices this
@@ -392,6 +428,18 @@ int fcpt_set_body_irradiation(fcpt_ctx *ctx, int32_t n, const double *temperatur
  * Blocks until the four sums are on the host. */
 int fcpt_disk_on_body_accel(fcpt_ctx *ctx, double x, double y, double r_object, double smoothing_fixed,
                             double cubic_smoothing_radius, double out[4]);
+
+/* The same four sums for n <= FCPT_MAX_BODIES objects from ONE pass over the slab's active rings (the density, and
+ * the energy or scale-height grid where a body asks for cell-wise smoothing, are read once for all bodies); body k is
+ * defined by (x[k], y[k], r_object[k], smoothing_fixed[k], cubic_smoothing_radius[k]) exactly as in the single-body
+ * call, whose kernel is mirrored cell by cell and sum by sum: out[4k .. 4k+3] carries the bits that call returns.
+ * _begin queues the pass and an asynchronous copy of the 4n sums into pinned host memory on the context's stream and
+ * returns; _end waits for that copy alone (an event) and hands out the sums of this slab.  A host-stepped loop queues
+ * _begin in front of fcpt_cfl, whose wait then covers both.  FCPT_EINVAL: n outside 1 .. FCPT_MAX_BODIES, _end
+ * without a pending _begin.  The caller adds the slabs' sums with fcpt_allreduce_sum. */
+int fcpt_disk_on_bodies_begin(fcpt_ctx *ctx, int32_t n, const double *x, const double *y, const double *r_object,
+                              const double *smoothing_fixed, const double *cubic_smoothing_radius);
+int fcpt_disk_on_bodies_end(fcpt_ctx *ctx, double *out /* 4n */);
 
 /* After the initial Sigma/v/energy upload: init_euler (src/SourceEuler.cpp:251-285:
  * sound speed, pressure, temperature, scale height, viscosity), the first
@@ -516,6 +564,14 @@ int fcpt_exchange(fcpt_ctx *ctx);
  * fcpt_calculate_timestep_device(ctx, NULL) picks it up.  With dt_global != NULL the call blocks and also
  * returns the value.  fcpt_run_steps uses both calls when the context has a communicator. */
 int fcpt_cfl_allreduce(fcpt_ctx *ctx, double *dt_global);
+
+/* ComputeDiskOnPlanetAccel's MPI_Allreduce(SUM) (src/Force.cpp:115): values[k] (host memory, in place, n <= 4 *
+ * FCPT_MAX_BODIES) becomes the sum over the slabs of the communicator, the same bits on every slab -- each slab kicks
+ * its own copy of the bodies with it.  Host-staged transport: every slab adds the slabs' values in rank order.  RCCL:
+ * one ncclAllReduce(ncclSum), which hands every rank the one reduced value (this branch needs several GPUs and has not
+ * been executed on the one-GPU machines the tests run on, like the rest of the RCCL path).  Blocks.  Without a
+ * communicator: FCPT_OK, values untouched. */
+int fcpt_allreduce_sum(fcpt_ctx *ctx, int32_t n, double *values);
 
 /* The rest of step_Euler after CommunicateBoundaries (src/simulation.cpp:244-265):
  * apply_boundary_condition(final=true) (damping first) and
