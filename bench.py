@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: cell-updates/s of the per-timestep gas update on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is one full hydro step (CFL reduction, source + viscosity substeps, boundary
 rings, FARGO transport, ghost exchange, derived quantities) of the 2048 x 4096
@@ -10,9 +10,15 @@ config 2 at the grid the metric is quoted on).  With N > 1 every rank owns 2048 
 (weak scaling; the log grid is extended outward so dr/r stays constant), neighbours
 exchange 7 ghost rings per step and the CFL step is MIN-reduced over the slabs -- both
 inside the library over RCCL (fcpt_comm_init / fcpt_run_steps), one process per GPU.
-An N > 1 run then also times BASELINE config 4 (2048 x 6144, the fixed domain split over the
-N slabs: strong scaling) and reports it as the extra row `strong_scaling`; `--scaling strong`
-makes that workload the headline of the line instead.
+`--scaling strong` makes BASELINE config 4 (2048 x 6144, the fixed domain split over the N slabs) the headline
+of the line instead.
+
+A plain run does what the headline figure needs and nothing else: set-up, the settle and warm-up steps, the K
+timed steps, the dump if `--dump-outputs` is given, the result line.  `--full` adds everything else the benchmark
+measures or checks, each in a run of its own around the same timed region: the CPU oracle timed on the host cores
+and compared with the HIP path (`cpu_baseline`), the table of the other BASELINE configurations (`configs`), the
+K-step blocks timed again after the timed region (`ms_per_step_blocks`) and, at N > 1, BASELINE config 4 as the
+strong-scaling row (`strong_scaling`).  The headline and the dump are the same with and without it.
 
 Ranks: under `python -m torch.distributed.run` the ranks are the launcher's (RANK,
 LOCAL_RANK, WORLD_SIZE, MASTER_* from the environment).  Started plainly with --gpus N > 1,
@@ -89,10 +95,16 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (the headline): --nr rings per GPU; strong: BASELINE config 4, the 2048x6144 grid "
-                         "split over the --gpus slabs (at N > 1 the weak line carries it as the row strong_scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the table of the other BASELINE configurations")
-    ap.add_argument("--no-strong-row", action="store_true", help="N > 1: skip the strong-scaling row (config 4)")
+                         "split over the --gpus slabs (at N > 1 the weak line of --full carries it as the row strong_scaling)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU oracle's baseline and parity check, the table of the other "
+                         "BASELINE configurations, the settle blocks and (N > 1) the strong-scaling row -- tens of "
+                         "seconds more; the --no-* options and --settle-blocks choose among them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle's baseline and parity check")
+    ap.add_argument("--no-configs", action="store_true",
+                    help="with --full: skip the table of the other BASELINE configurations")
+    ap.add_argument("--no-strong-row", action="store_true",
+                    help="with --full, N > 1: skip the strong-scaling row (config 4)")
     ap.add_argument("--nr", type=int, default=NR_PER_GPU, help="rings per GPU")
     ap.add_argument("--nphi", type=int, default=NPHI)
     ap.add_argument("--eos", choices=["isothermal", "ideal"], default="isothermal",
@@ -104,7 +116,7 @@ def parse_args():
                     help="with --rehearse-exchange: which slab of how many (the weak-scaling geometry of N GPUs; an inner "
                          "or outer slab talks to itself on its one neighbour side only)")
     ap.add_argument("--settle-blocks", type=int, default=4,
-                    help="after the timed region: this many more blocks of --steps steps, timed one by one "
+                    help="with --full, after the timed region: this many more blocks of --steps steps, timed one by one "
                          "(reported as ms_per_step_blocks: shows a clock ramp over a short timed region)")
     ap.add_argument("--transport", choices=["rccl", "host"], default="rccl",
                     help="host: REHEARSAL of the N-rank line on fewer GPUs than ranks -- the ranks share the visible GPU(s), the "
@@ -457,9 +469,9 @@ def main():
 
     # ---- parity leg, device half: the same workload on a second context, PARITY_STEPS steps from the same initial
     # state; the oracle repeats them on the host cores after the timed region and the two end states are compared
-    # (cpu_baseline.parity_max_rel).  Queued here, ahead of the settle steps.
+    # (cpu_baseline.parity_max_rel).  Queued here, ahead of the settle steps.  (--full only.)
     parity_ctx = None
-    if world == 1 and not rehearse and not args.no_cpu_baseline:
+    if args.full and world == 1 and not rehearse and not args.no_cpu_baseline:
         parity_ctx = driver.make_context(lib, d, fields=leg.fields, radii=leg.radii, bodies=leg.bodies)
         parity_ctx.set_stream(torch.cuda.current_stream().cuda_stream)
         for _ in range(2):
@@ -501,9 +513,9 @@ def main():
     if args.dump_outputs:   # before the blocks below step on
         dumped = dump_outputs(args.dump_outputs, leg.outputs(), ctx.clock, prefix=f"rank{rank}_" if multi else "")
 
-    # the same block again, a few times: a timed region of K x 0.4 ms can end before the GPU clocks have settled
+    # --full: the same block again, a few times: a timed region of K x 0.4 ms can end before the GPU clocks have settled
     blocks = []
-    for _ in range(max(0, args.settle_blocks)):
+    for _ in range(max(0, args.settle_blocks) if args.full else 0):
         leg.sync()
         b0 = time.perf_counter()
         leg.run(args.steps)
@@ -524,7 +536,7 @@ def main():
 
     # ---- N > 1: BASELINE config 4 as the strong-scaling row (every rank takes part) ----------------------------------
     strong_row = None
-    if multi and not strong and not args.no_strong_row:
+    if args.full and multi and not strong and not args.no_strong_row:
         strong_row = strong_scaling_row(env, args, setups, np)
 
     if rank == 0:
@@ -543,7 +555,7 @@ def main():
             workload = f"{nr_total}x{nphi} {physics}, {args.nr} rings per GPU"
         out = {
             "metric": "cell-updates/s on Nr x Nphi polar grid", "value": value, "unit": "cell-updates/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": bool(args.full),
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": args.scaling,
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": workload,
@@ -579,7 +591,7 @@ def main():
                                            "and ran untimed_steps_before_timed_region steps from there"}
         if strong_row is not None:
             out["strong_scaling"] = strong_row
-        if world == 1 and not rehearse and not args.no_configs:
+        if args.full and world == 1 and not rehearse and not args.no_configs:
             out["configs"] = config_table(env, args, setups)
         if parity_ctx is not None:
             hip_state = parity_ctx.state()

@@ -22,8 +22,8 @@ python3 profiles/make_pmc_json.py $O/pmc_ideal profiles/r03_ideal_eos_pmc_summar
 find $O/pmc $O/pmc_ideal -name "*kernel_trace.csv" -delete
 find $O/pmc $O/pmc_ideal -name "*counter_collection.csv" -delete
 echo "[4] bench lines"
-timeout -k 10 400 python3 bench.py --steps 200 --warmup 20 > $O/bench.json 2> $O/bench.err || echo "bench failed"
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-configs > $O/bench_driver_form.json 2> $O/bench_driver_form.err || echo "bench (driver form) failed"
-timeout -k 10 300 python3 bench.py --steps 100 --warmup 10 --eos ideal --no-cpu-baseline --no-configs > $O/bench_ideal.json 2> $O/bench_ideal.err || echo "bench ideal failed"
-timeout -k 10 300 python3 bench.py --steps 100 --warmup 10 --rehearse-exchange > $O/bench_rehearse.json 2> $O/bench_rehearse.err || echo "bench rehearse failed"
+timeout -k 10 400 python3 bench.py --steps 200 --warmup 20 --full > $O/bench.json 2> $O/bench.err || echo "bench failed"
+timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $O/bench_driver_form.json 2> $O/bench_driver_form.err || echo "bench (driver form) failed"
+timeout -k 10 300 python3 bench.py --steps 100 --warmup 10 --eos ideal --full --no-cpu-baseline --no-configs > $O/bench_ideal.json 2> $O/bench_ideal.err || echo "bench ideal failed"
+timeout -k 10 300 python3 bench.py --steps 100 --warmup 10 --rehearse-exchange --full > $O/bench_rehearse.json 2> $O/bench_rehearse.err || echo "bench rehearse failed"
 ls -la $O | head -40

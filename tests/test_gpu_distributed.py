@@ -164,7 +164,7 @@ def test_bench_n_rank_line_rehearsed_on_one_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["FCPT_BENCH_SETTLE_STEPS"], env["FCPT_BENCH_SETTLE_MS"] = "10", "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--transport", "host", "--steps", "6",
-                        "--warmup", "2", "--nr", "64", "--nphi", "512", "--settle-blocks", "1"], env=env, capture_output=True,
+                        "--warmup", "2", "--nr", "64", "--nphi", "512", "--settle-blocks", "1", "--full"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
