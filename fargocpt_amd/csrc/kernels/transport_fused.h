@@ -145,7 +145,7 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
     double w[3][NQ];  // specific quantities: Sigma, v_r(ring+1), v_r(ring), (v_phi(j+1) + r Omega) r, (v_phi + r Omega) r(, e / Sigma)
     double er[3];     // the energy itself (!DIET)
     double vp[3];     // v_phi as loaded (!DVP)
-    double d1[NQ];    // (w(m-1) - w(m-2)) InvDiffRmed[m-1] (!DIET)
+    double d1[NQ];    // (w(m-1) - w(m-2)) InvDiffRmed[m-1] (!DIET; not of slot 3, whose slope comes from the next lane)
     double idr_prev = 0.0; // DIET: InvDiffRmed[m-1], to re-form d1
     double hs1[NQ];   // limited half slope of ring m-2
     double F1[NQ];    // flux through interface m-2
@@ -184,12 +184,11 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
     // (r, romega: Rmed[k] and Rmed[k] OmegaFrame, from the caller's batch of per-ring scalars)
     auto convert = [&](int k, const RingRaw &o, double r, double romega) {
         const bool in_k = k >= 0 && k < nr;
-        const double van = lane_next(o.va); // v_phi of cell j+1
         w[0][0] = o.sg;
         w[0][1] = in_k ? o.vr : 0.0;                        // rm+ / Sigma = v_r(k+1)   (:484-485)
         w[0][2] = in_k ? vr_last : 0.0;                     // rm- / Sigma = v_r(k)
-        w[0][3] = in_k ? (van + romega) * r : 0.0;          // L+ / Sigma = (v_phi(j+1) + r Omega) r
         w[0][4] = in_k ? (o.va + romega) * r : 0.0;         // L- / Sigma
+        w[0][3] = lane_next(w[0][4]);                       // L+ / Sigma = (v_phi(j+1) + r Omega) r: L- / Sigma of cell j+1
         if (ADI) {
             w[0][NQ - 1] = in_k ? o.en * FAST_RCP_TR(o.sg) : 0.0;
             if (!DIET)
@@ -248,13 +247,25 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
             const bool up = v > 0.0;
             const double dist = up ? (rk.dr_lo - v * dt) : -(rk.dr_hi + v * dt);
             double Fc;
+            double hs0[NQ]; // limited half slopes of ring m-1
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
+                if (q == 3)
+                    continue;
                 const double d0 = (w[0][q] - w[1][q]) * idr_m;
                 const double dprev = DIET ? (w[1][q] - w[2][q]) * idr_prev : d1[q];
-                const double hs0 = lim_ok ? half_limiter(lim, d0, dprev) : 0.0; // ring m-1
+                hs0[q] = lim_ok ? half_limiter(lim, d0, dprev) : 0.0;
+                if (!DIET)
+                    d1[q] = d0;
+            }
+            // Slot 3 of a lane is slot 4 of the lane to its right in all three rings of the window, bit for bit
+            // (convert()), and so are its differences and its limited slope: one lane shift instead of a second
+            // half_limiter (lane 63, which has no right-hand lane, is halo: "right 1" above)
+            hs0[3] = lane_next(hs0[4]);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
                 // (both candidates with the lane's own distance, then one select: see theta_star)
-                const double st_up = w[2][q] + dist * hs1[q], st_dn = w[1][q] + dist * hs0;
+                const double st_up = w[2][q] + dist * hs1[q], st_dn = w[1][q] + dist * hs0[q];
                 const double st = up ? st_up : st_dn;
                 if (q == 0) {
                     Fc = open ? g * st * w[1][2] : 0.0; // mass flux g rho* v
@@ -262,9 +273,7 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
                 } else {
                     F0[q] = st * Fc;
                 }
-                if (!DIET)
-                    d1[q] = d0;
-                hs1[q] = hs0;
+                hs1[q] = hs0[q];
             }
         }
         // ---- update of ring i = m-2, azimuthal passes, velocities -----------------------------
