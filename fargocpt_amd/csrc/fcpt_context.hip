@@ -174,7 +174,7 @@ void apply_options(fcpt_ctx *c, bool at_create = true)
     c->P.sm_sched_n = 0;
     c->sm_sched_host.clear();
     if (c->sm_sched_dev && c->fused_source && c->march_source) {
-        const std::vector<int> sched = source_schedule(c->P);
+        const std::vector<int> sched = source_schedule(c->P, device_cus());
         if (!sched.empty() && sched.size() <= c->sm_sched_cap &&
             hipMemcpy(c->sm_sched_dev, sched.data(), sched.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) {
             c->P.sm_sched = c->sm_sched_dev;
@@ -189,7 +189,7 @@ void apply_options(fcpt_ctx *c, bool at_create = true)
         std::vector<int> slow(c->P.nr, 0);
         if (c->P.damp_in_step)
             slow = c->ring_ref_damped;
-        const std::vector<int> sched = transport_schedule(c->P, slow, &c->tf_lengths);
+        const std::vector<int> sched = transport_schedule(c->P, device_cus(), slow, &c->tf_lengths);
         c->tf_sched_host.clear();
         if (!sched.empty() && sched.size() <= c->tf_sched_cap &&
             hipMemcpy(c->tf_sched_dev, sched.data(), sched.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) {

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fcpt_internal.h"
+#include "fcpt_schedule.h"
 
 namespace fcpt {
 
@@ -74,11 +75,7 @@ struct GatedTheta {
 void launch_gated_theta(const GatedTheta &g, const Dev *boundary_view, hipStream_t st); // boundary_view != null: + the boundary call, one launch
 enum { TRANSPORT_ALL = 0, TRANSPORT_EDGES = 1, TRANSPORT_INTERIOR = 2 };
 TransportResult launch_transport(const Dev &P, const Dev &W, hipStream_t st, int part = TRANSPORT_ALL, GatedTheta *defer_gated = nullptr);
-bool transport_can_split(const Dev &P, bool shear_safe);
-std::vector<int> source_schedule(const Dev &P);
-void selftest_chunk_tables(int nr, int nphi, int n_cu, int adiabatic, int damp_inner, int damp_outer, const Options &opt,
-                           std::vector<int> &transport, std::vector<int> &source);
-std::vector<int> transport_schedule(const Dev &P, const std::vector<int> &slow_rings, const std::vector<int> *lengths);
+int device_cus(); // compute units of the current device: the argument n_cu of the chunk planner (fcpt_schedule.h)
 void launch_shift_means(const Dev &P, hipStream_t st);
 void launch_massflow(const Dev &P, hipStream_t st);
 void launch_substep3_cooling_only(const Dev &P, hipStream_t st);
@@ -92,7 +89,6 @@ size_t disk_on_bodies_blocks(const Dev &P); // blocks of the first stage: `part`
 void launch_disk_on_bodies(const Dev &P, int n, const DiskBodies &B, double *part, double *out, hipStream_t st);
 void launch_source_fused(const Dev &P, hipStream_t st);
 int launch_source_march(const Dev &P, hipStream_t st, bool fold_bc, bool *bc_folded, bool fold_cfl = false);
-bool source_march_applies(const Dev &P);
 void launch_cfl_final(const Dev &P, int apply_policy, hipStream_t st);
 bool cfl_by_rings(const Dev &P);
 void launch_viscous_fused(const Dev &P, hipStream_t st);

@@ -175,7 +175,7 @@ void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool spl
         launch_clock_scale_dt(P.clk, 2, 0.0, 1.0, st); // dt <- step (saved in cfl_dt)
     launch_massflow(Q, st); // WriteMassFlow: what this Transport() carries through the interfaces
     TransportResult tr;
-    if (split && !frog && transport_can_split(Q, shear_safe) && c->side) {
+    if (split && !frog && transport_can_split(Q, device_cus(), shear_safe) && c->side) {
         launch_shift_means(Q, st);
         (void)hipEventRecord(c->e_fork, st);
         (void)hipStreamWaitEvent(c->side, c->e_fork, 0);

@@ -7,7 +7,7 @@
 // min_cells dt_cell == CFL / sqrt(max_cells sum): k_cfl_cells reduces the per-cell sums to one
 // maximum per block (no atomics); k_cfl_final folds the block maxima, applies sqrt and the
 // quotient once, and adds the per-ring FARGO shear limit (:207-220).
-#define CFL_ROWS 8 /* on grids that fill the GPU; fewer on small ones (march_len, launch.h) */
+#include "../fcpt_schedule.h" // CFL_ROWS, shared with the chunk planner
 // One thread owns a phi column and walks CFL_ROWS rings (v_r(i+1) of one ring is v_r(i) of the
 // next, so every value is loaded once); per-block maxima, no atomics.
 template <bool ROWU> __global__ void k_cfl_cells(const Dev P, double *part, int rows)

@@ -37,7 +37,7 @@
 // loads by 32-bit offset, stores by index: with the stores by offset too the 128-register kernel spills 12 bytes and loses 14 us
 #define ADI_LD(g_, r_) ld_off(g_, MOFF(r_))
 #define ADI_ST(g_, r_, v_) (g_)[IDX(r_, j)] = (v_)
-#define MARCH_VALID 59
+#include "../fcpt_schedule.h" // MARCH_VALID (59), shared with the chunk planner
 #define MARCH_LO 3
 
 // StabilizeViscosity (viscosity.cpp:256-348): the correction factors c1_phi, c1_r of ring k -- the diagonal of the

@@ -90,7 +90,6 @@ template <bool ROWU> __global__ void k_massflow(const Dev P)
 // is evaluated once and each ring is loaded once per chunk (+4 halo rings).
 // The specific momenta Work = (Sigma v)/Sigma are formed as v directly (equal to
 // the reference's quotient to within 1 ulp).
-#define RADIAL_ROWS 16 /* rings per thread on grids that fill the GPU; fewer on small ones (march_len, launch.h) */
 
 struct RadialRow { // specific quantities of one ring at this column (er: the energy itself)
     double s, rmp, rmm, lp, lm, e, er;
@@ -533,7 +532,7 @@ template <bool DAMP, bool ROWU> __global__ void k_velocities(const Dev P, ThetaS
 // cell for a one-launch azimuthal sweep + k_velocities.
 // Validity: 4 cells at either end of a segment are lost to the two passes, one more on the
 // left to the L+(j-1) neighbour.
-#define THETA_ROWS 8
+#include "../fcpt_schedule.h" // RADIAL_ROWS, THETA_ROWS, shared with the chunk planner
 #define THETA_LO 6 /* even, so that a lane's two cells are both final or both halo */
 #define THETA_HI 4
 

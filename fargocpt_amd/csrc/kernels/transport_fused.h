@@ -26,16 +26,13 @@
 // The chunks of one launch: `count` of them, the first `lead` are chunks 0..lead-1 of the grid, the others follow
 // `skip` chunks further up.  All chunks at once: {n, n, 0, 1}.  Slabs with neighbours march the chunks that hold
 // the rings the neighbours are waiting for first (fcpt_step_device_begin): {1 + tail, 1, gap, 1} then {gap, 0, 1, 0}.
-#define TF_XCD_CHUNKS 16 /* launches of at least this many chunks deal whole chunks to the XCDs */
 // sched != null: wavefront w of the launch (blockIdx.x * 4 + its index in the workgroup) marches tile sched[4w] over rings
-// [sched[4w+1], sched[4w+2]) -- transport_schedule() in launch.h; count = entries, lead / skip do not apply.
+// [sched[4w+1], sched[4w+2]) -- transport_schedule() in fcpt_schedule.cpp; count = entries, lead / skip do not apply.
+#include "../fcpt_schedule.h" // TF_XCD_CHUNKS, TF_HALO_LO, TF_HALO_HI, TF_STRIDE, shared with the chunk planner
 struct TfChunks {
     int count, lead, skip, advance_clock;
     const int *sched;
 };
-#define TF_HALO_LO 5 /* cells of a 64-column segment that are not final: left ... */
-#define TF_HALO_HI 6 /* ... and right */
-#define TF_STRIDE (64 - TF_HALO_LO - TF_HALO_HI) /* columns a wavefront stores: tiles of 53 */
 
 // wave damping with the ring's precomputed exp(-dt f / tau) (k_ring_mean): types as damp_value.  The load of the
 // reference value and its use sit in one basic block: a load whose use is behind another branch leaves the compiler's

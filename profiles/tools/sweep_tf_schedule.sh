@@ -1,6 +1,6 @@
 #!/bin/bash
 # ms per step and kernel times of the headline workload for explicit chunk-length lists of k_transport_fused
-# (FCPT_TF_SCHEDULE, see transport_schedule() in kernels/launch.h); "uniform" = equal chunks, "auto" = the built-in grading.
+# (FCPT_TF_SCHEDULE, see transport_schedule() in fcpt_schedule.cpp); "uniform" = equal chunks, "auto" = the built-in grading.
 # usage: profiles/tools/sweep_tf_schedule.sh "<spec> <spec> ..." [extra bench args]   (run on the GPU box)
 SPECS=$1; shift
 for v in uniform auto $SPECS; do

@@ -193,7 +193,7 @@ def test_bench_loop_is_reproducible_bit_for_bit(product, adiabatic):
 @pytest.mark.parametrize("adiabatic", [False, True])
 def test_graded_transport_chunks_at_full_size(product, adiabatic):
     """At the bench size the fused transport needs two rounds of the GPU's wavefront slots, and the library grades its
-    chunk lengths (transport_schedule in kernels/launch.h): the table must hold every ring exactly once, start with
+    chunk lengths (transport_schedule in fcpt_schedule.cpp): the table must hold every ring exactly once, start with
     the same number of long chunks for each of the 8 XCDs, end with short ones -- and give the bits of equal chunks."""
     d = setups.planet_disk(product, NR, NPHI, adiabatic=adiabatic)
     d0 = d.copy()
@@ -237,7 +237,7 @@ def test_graded_transport_chunks_at_full_size(product, adiabatic):
 @pytest.mark.parametrize("adiabatic", [False, True])
 def test_rank_matched_source_chunks_at_full_size(product, adiabatic):
     """The marching source kernels run as one round of wavefronts at the bench size; the library matches every
-    wavefront's chunk length to the rank at which its SIMD will serve it (source_schedule in kernels/launch.h).  The
+    wavefront's chunk length to the rank at which its SIMD will serve it (source_schedule in fcpt_schedule.cpp).  The
     table must hold every (segment, ring) exactly once, give the first wavefronts of an XCD longer chunks than its last,
     and give the bits of equal chunks (every ring of a segment is computed by one wavefront from the same operands; the
     ring sums of v_phi are per segment)."""

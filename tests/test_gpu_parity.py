@@ -941,3 +941,23 @@ def test_boundary_call_inside_the_cfl_launch(product, case):
     assert states[0][1] == states[1][1]
     for k in states[0][0]:
         assert np.array_equal(states[0][0][k], states[1][0][k]), k
+
+
+@pytest.mark.parametrize("adiabatic", [False, True])
+def test_context_chunk_tables_are_the_planners_for_this_device(product, adiabatic):
+    """The chunk planner (fcpt_schedule.cpp) takes the device's compute units as an argument; the HIP unit queries them
+    once and hands them in.  The tables a 2048 x 4096 context holds (no step is run) must be the ones the host-only
+    hook computes for that count -- the same code that tests/test_chunk_tables_golden.py pins byte for byte.  No wave
+    damping: 0 damped rings at either end on both sides."""
+    import torch
+    from fargocpt_amd import driver
+    n_cu = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+    d = setups.planet_disk(product, 2048, 4096, adiabatic=adiabatic, damping=False)
+    ctx = driver.make_context(product, d, bodies=setups.jupiter_bodies(d))
+    try:
+        transport, source = product.selftest_chunk_tables(2048, 4096, n_cu, adiabatic, 0, 0)
+        assert len(transport) and len(source)
+        assert np.array_equal(ctx.transport_chunks(), transport)
+        assert np.array_equal(ctx.source_chunks(), source)
+    finally:
+        ctx.close()

@@ -211,7 +211,7 @@ def test_option_names_are_documented():
     doc = hdr[hdr.index("Kernel-selection switches of one context"):hdr.index("int fcpt_set_option")]
     missing = [n for n in names if not re.search(r"\b%s\b" % n, doc)]
     assert not missing, missing
-    for f in ("kernels/launch.h", "fcpt_step.hip", "fcpt_exchange.hip"):
+    for f in ("kernels/launch.h", "fcpt_schedule.cpp", "fcpt_step.hip", "fcpt_exchange.hip"):
         assert "getenv" not in open(os.path.join(ROOT, "fargocpt_amd", "csrc", f)).read(), f
 
 
@@ -240,7 +240,7 @@ def test_rank_launcher_of_the_host_driver_reports_and_cleans_up(tmp_path):
                                                     (1024, 3072, True, 50), (4096, 4096, False, 0), (1367, 2731 * 2, True, 33),
                                                     (512, 1536, False, 20), (128, 384, False, 0), (100, 2, False, 0)])
 def test_chunk_tables_of_the_marching_kernels(product, nr, nphi, adiabatic, damp):
-    """transport_schedule / source_schedule (kernels/launch.h) as host logic for an MI355X (256 CUs): whatever the
+    """transport_schedule / source_schedule (fcpt_schedule.cpp) as host logic for an MI355X (256 CUs): whatever the
     grid, a table that is handed to the kernels holds every ring (every (segment, ring)) exactly once, no chunk is
     empty, the long chunks come first; small grids get no table (equal chunks)."""
     t, s = product.selftest_chunk_tables(nr, nphi, 256, adiabatic, damp, damp)
