@@ -34,19 +34,14 @@ struct TfChunks {
     const int *sched;
 };
 
-// wave damping with the ring's precomputed exp(-dt f / tau) (k_ring_mean): types as damp_value.  The load of the
-// reference value and its use sit in one basic block: a load whose use is behind another branch leaves the compiler's
-// s_waitcnt pass with a "maybe pending" register at every later store of the loop, and the pinned prefetch (bottom
-// of the loop) would be waited for on the spot again.
-__device__ __forceinline__ double damp_apply(double X, int type, double ef, const double *ref, unsigned cell_off, double zero_target)
+// wave damping with the ring's precomputed exp(-dt f / tau) (k_ring_mean): types as damp_value, X0 the reference value
+// of the cell.  The types are wave-uniform and only select: no branch, so that the loads of a ring's reference values
+// and all their uses stay in one basic block (see the damped form of new_state in transport_fused_body).
+__device__ __forceinline__ double damp_select(double X, int type, double ef, double X0, double zero_target)
 {
-    if (type == 1) {
-        const double X0 = ld_off(ref, cell_off);
-        return (X - X0) * ef + X0;
-    }
-    if (type != 0)
-        return (X - zero_target) * ef + zero_target;
-    return X;
+    const double target = type == 1 ? X0 : zero_target;
+    const double damped = (X - target) * ef + target;
+    return type != 0 ? damped : X;
 }
 
 template <bool ADI, bool DAMP, int LIM>
@@ -70,9 +65,9 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
     const int lane = threadIdx.x & 63;
     // Chunks are dealt to the 8 XCDs round-robin (workgroup b runs on XCD b % 8; all tiles of a chunk on one XCD, whose
     // L2 then serves their shared halo columns), in an order that starts at both ends of the slab and works inward:
-    // the rings of the damping zones cost ~1.5x (three more loads per cell, waited for on the spot), and with the
-    // chunks in radial order on contiguous XCD ranges the outer zone's wavefronts started last, on one XCD, and ran
-    // on alone (2.98 of 4 wavefronts per SIMD on average; -5.5 % kernel time, -3 % / -4.6 % per step, three A/B pairs).
+    // the rings of the damping zones cost more (three more loads per cell; ~1.5x while each was waited for on the spot:
+    // the figure of the measurements quoted here), and with the chunks in radial order on contiguous XCD ranges the
+    // outer zone's wavefronts started last, on one XCD, and ran on alone (2.98 of 4 wavefronts per SIMD on average; -5.5 % kernel time, -3 % / -4.6 % per step, three A/B pairs).
     // (launches of fewer than TF_XCD_CHUNKS chunks -- short slabs -- deal workgroups instead: every XCD gets work)
     if (ch.advance_clock && blockIdx.x == 0 && threadIdx.x == 0) { // sim::time += dt; N_hydro_iter++ (simulation.cpp:226-227)
         clock_advance(W.clk, P.clk->dt);
@@ -322,21 +317,43 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
                 const unsigned row = (unsigned)i * (unsigned)nphi;
                 int jo = jin + ns;
                 const int jout = jo >= nphi ? jo - nphi : jo;
-                double vr = 0.0;
-                if (i != 0)
-                    vr = (rp + Q[1][0]) * FAST_RCP_TR(sp + S[0]);
-                double va = (lpm + Q[3][0]) * FAST_RCP_TR(sm + S[0]) * invr - romega;
-                double sf = S[0] < P.sigma_floor_abs ? P.sigma_floor_abs : S[0];
-                double e = ADI ? clamp_energy_fast(P, E[0], sf) : 0.0;
                 const unsigned g = (row + (unsigned)jout) * 8u;
-                if (DAMP) {
-                    vr = damp_apply(vr, di.tvr, si.ev, W.vrad0, g, 0.0);
-                    va = damp_apply(va, di.tva, si.es, W.vazi0, g, 0.0);
-                    sf = damp_apply(sf, di.tsg, si.es, W.sigma0, g, W.sigma_floor_abs);
-                    if (ADI)
-                        e = damp_apply(e, di.ten, si.es, W.energy0, g, 0.0);
-                }
-                o_vr = vr, o_va = va, o_s = sf, o_e = e;
+                // Velocities from momenta, floors, wave damping.  A ring of the damping zones -- any quantity of a type
+                // other than 0 -- requests the reference values of all its quantities at once, ahead of the
+                // reciprocals, and uses them behind: one memory round trip under the arithmetic instead of one per
+                // quantity at the end of it (a quantity of type 0 or 2 in such a ring loads its reference as well
+                // and drops it in damp_select).  The damped ring is a basic block of its own that holds the loads
+                // AND every use: a load whose use is behind another branch leaves the compiler's s_waitcnt pass with
+                // a "maybe pending" register at every later store of the loop, and the pinned prefetch (bottom of
+                // the loop) would be waited for on the spot again.  The other rings run the block without a load.
+                auto new_state = [&](const bool damped) {
+                    double vr0 = 0.0, va0 = 0.0, s0 = 0.0, e0 = 0.0;
+                    if (damped) {
+                        vr0 = ld_off(W.vrad0, g);
+                        va0 = ld_off(W.vazi0, g);
+                        s0 = ld_off(W.sigma0, g);
+                        if (ADI)
+                            e0 = ld_off(W.energy0, g);
+                    }
+                    double vr = 0.0;
+                    if (i != 0)
+                        vr = (rp + Q[1][0]) * FAST_RCP_TR(sp + S[0]);
+                    double va = (lpm + Q[3][0]) * FAST_RCP_TR(sm + S[0]) * invr - romega;
+                    double sf = S[0] < P.sigma_floor_abs ? P.sigma_floor_abs : S[0];
+                    double e = ADI ? clamp_energy_fast(P, E[0], sf) : 0.0;
+                    if (damped) {
+                        vr = damp_select(vr, di.tvr, si.ev, vr0, 0.0);
+                        va = damp_select(va, di.tva, si.es, va0, 0.0);
+                        sf = damp_select(sf, di.tsg, si.es, s0, W.sigma_floor_abs);
+                        if (ADI)
+                            e = damp_select(e, di.ten, si.es, e0, 0.0);
+                    }
+                    o_vr = vr, o_va = va, o_s = sf, o_e = e;
+                };
+                if (DAMP && (di.tvr | di.tva | di.tsg | (ADI ? di.ten : 0)) != 0)
+                    new_state(true);
+                else
+                    new_state(false);
                 out_g = g;
                 out_on = true;
             }
@@ -384,9 +401,10 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
             if (i == nr - 1 && valid) { // v_r row Nr is neither transported nor shifted: copied column by column
                 const unsigned gt = ((unsigned)nr * (unsigned)nphi + (unsigned)jin) * 8u;
                 double v = ld_off(P.vrad, gt);
-                if (DAMP) {
+                if (DAMP) { // (the reference value requested with the row itself, whatever the type: one round trip)
+                    const double v0 = ld_off(W.vrad0, gt);
                     const DampRow dn = crow_load(W.damp_tab, nr);
-                    v = damp_apply(v, dn.tvr, si.ev_top, W.vrad0, gt, 0.0);
+                    v = damp_select(v, dn.tvr, si.ev_top, v0, 0.0);
                 }
                 st_off(W.vrad, gt, v);
             }
