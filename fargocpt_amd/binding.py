@@ -104,6 +104,14 @@ class Clock(C.Structure):
                 ("n_monitor", _u32), ("n_snapshot", _u32)]
 
 
+class ParticleParams(C.Structure):
+    _fields_ = [("particle_density", _f64), ("molecule_mass", _f64), ("molecule_radius", _f64), ("k_B", _f64),
+                ("escape_radius_min", _f64), ("escape_radius_max", _f64), ("gravity_cartesian", _i32), ("_pad0", _i32)]
+
+
+PARTICLE_FIELDS = ("r", "phi", "r_dot", "phi_dot", "radius", "stokes")
+
+
 class FcptError(RuntimeError):
     pass
 
@@ -167,6 +175,11 @@ class Library:
         self.check(self.fn("initial_fields")(C.byref(d), _as_dp(radii), _as_dp(sigma), _as_dp(vrad),
                                              _as_dp(vazi), _as_dp(energy)), "initial_fields")
         return sigma, vrad, vazi, energy
+
+    def particle_params_default(self, d: Desc) -> ParticleParams:
+        p = ParticleParams()
+        self.check(self.fn("particle_params_default")(C.byref(d), C.byref(p)), "particle_params_default")
+        return p
 
     def kernel_names(self):
         n = self.fn("kernel_count")()
@@ -427,6 +440,36 @@ class Context:
         self.disk_on_bodies_begin(x, y, r_object, np.full(n, -1.0) if smoothing_fixed is None else smoothing_fixed,
                                   np.zeros(n) if cubic_smoothing_radius is None else cubic_smoothing_radius)
         return self.disk_on_bodies_end()
+
+    # dust particles (host-stepped loop: set_bodies, particles_step, step, post)
+    def particles_set(self, params: ParticleParams, ids, r, phi, r_dot, phi_dot, radius, stokes):
+        """Replace the context's particles (slot k = entry k, the caller's order is kept); empty arrays remove them."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        a = [np.ascontiguousarray(v, dtype=np.float64) for v in (r, phi, r_dot, phi_dot, radius, stokes)]
+        assert all(v.shape == ids.shape and v.ndim == 1 for v in a)
+        self._call("particles_set", C.byref(params), C.c_int64(ids.size), ids.ctypes.data_as(C.POINTER(_u64)),
+                   *(_as_dp(v) for v in a))
+
+    def particles_step(self, dt: float, indirect=(0.0, 0.0), frame_angle: float = 0.0):
+        """Queues the indirect-term kick, the exponential-midpoint step, the escape test and the frame's rotation."""
+        self._call("particles_step", _f64(dt), _f64(indirect[0]), _f64(indirect[1]), _f64(frame_angle))
+
+    def particles_count(self) -> int:
+        n = C.c_int64()
+        self._call("particles_count", C.byref(n))
+        return n.value
+
+    def particles_get(self) -> dict:
+        """The live particles in ascending slot order: {"id": uint64[n], "r", "phi", "r_dot", "phi_dot", "radius", "stokes": float64[n]}."""
+        cap = self.particles_count()
+        ids = np.zeros(cap, dtype=np.uint64)
+        a = {k: np.zeros(cap) for k in PARTICLE_FIELDS}
+        n = C.c_int64()
+        self._call("particles_get", C.c_int64(cap), ids.ctypes.data_as(C.POINTER(_u64)), *(_as_dp(a[k]) for k in PARTICLE_FIELDS),
+                   C.byref(n))
+        out = {"id": ids[:n.value].copy()}
+        out.update({k: v[:n.value].copy() for k, v in a.items()})
+        return out
 
     def allreduce_sum(self, values) -> np.ndarray:
         """SUM over the slabs of the communicator (the same bits on every slab); without one: the input."""

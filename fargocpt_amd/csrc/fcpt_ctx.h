@@ -1,7 +1,7 @@
 // Shared by the translation units of the device side of the C ABI: the context structure and the helpers that more
 // than one of them uses.  fcpt_context.hip: creation, options, transfers, initial physics, profiling;
 // fcpt_step.hip: CFL, the step, the final boundary call, the run loop (+ hipGraph replay);
-// fcpt_exchange.hip: ghost exchange and the RCCL entry points.
+// fcpt_exchange.hip: ghost exchange and the RCCL entry points; fcpt_particles.hip: dust particles.
 #ifndef FCPT_CTX_H
 #define FCPT_CTX_H
 
@@ -101,6 +101,11 @@ struct fcpt_ctx {
     hipStream_t comm_stream = nullptr;
     hipEvent_t e_packed = nullptr, e_received = nullptr;
     int device = 0; // HIP device the context was created on
+    // dust particles (fcpt_particles.hip): device arrays and parameters of k_particles_step (part.n = 0: none), the ids
+    // by slot, the one device block behind all of them
+    ParticleArgs part = {};
+    unsigned long long *part_id = nullptr;
+    void *part_block = nullptr;
     // fcpt_run_steps on launch-bound grids: a captured hipGraph of `graph_cycle` consecutive steps (the out-of-place
     // transport swaps grid pointers, so the launch arguments repeat with period 2), replayed while the host-side state
     // that decided the launches (the whole Dev view, the lazy-evaluation flags) is what it was at capture
@@ -169,6 +174,8 @@ void enqueue_cfl(fcpt_ctx *c, int apply_policy);
 void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool split = false);
 void enqueue_post(fcpt_ctx *c, bool may_defer_boundary = false);
 void flush_deferred_boundary(fcpt_ctx *c);
+// fcpt_particles.hip
+void particles_free(fcpt_ctx *c);
 // fcpt_exchange.hip
 int enqueue_exchange(fcpt_ctx *c);
 int enqueue_cfl_allreduce(fcpt_ctx *c);

@@ -392,6 +392,29 @@ int fcpt_desc_default(fcpt_desc *d)
     return FCPT_OK;
 }
 
+// parameters.cpp:853-961 and calc_tstop's constants (particles/particles.cpp:1139-1147) in the units of fcpt_desc_default
+int fcpt_particle_params_default(const fcpt_desc *d, fcpt_particle_params *out)
+{
+    if (!d || !out) {
+        set_error("null argument");
+        return FCPT_EINVAL;
+    }
+    const double G_cgs = 6.67430e-8, kB = 1.380649e-16, mu_cgs = 1.66053906660e-24;
+    const double L0 = 1.495978707e13, M0 = 1.988409870698051e33;
+    const double T0 = std::sqrt(L0 * L0 * L0 / (G_cgs * M0));
+    const double Temp0 = G_cgs * mu_cgs / kB * M0 / L0;
+    const double E0 = M0 * L0 * L0 / (T0 * T0);
+    std::memset(out, 0, sizeof(*out));
+    out->particle_density = 2.65 / (M0 / (L0 * L0 * L0)); // "2.65 g/cm3"
+    out->molecule_mass = d->mu * (mu_cgs / M0);
+    out->molecule_radius = 1.5e-8 / L0;
+    out->k_B = kB / (E0 / Temp0);
+    out->escape_radius_min = d->rmin;
+    out->escape_radius_max = d->rmax;
+    out->gravity_cartesian = 0;
+    return FCPT_OK;
+}
+
 int fcpt_split_domain(const fcpt_desc *d, fcpt_split *out)
 {
     if (!d || !out) {

@@ -274,6 +274,24 @@ struct Dev {
     Options opt; // host side only: which kernels the launchers pick
 };
 
+// what a launch of k_particles_step needs besides the Dev view (kernels/particles.h; filled by fcpt_particles.hip)
+struct ParticleArgs {
+    int n;
+    double *r, *phi, *r_dot, *phi_dot, *stokes;
+    const double *radius;
+    unsigned char *alive;
+    unsigned long long *status; // 0: clean; else guard number | slot << 8 of a particle that tripped a guard
+    double particle_density, molecule_mass, molecule_radius, k_B;
+    double escape_min_sq, escape_max_sq;
+    int gravity_cartesian;
+    // first guess of the cell search (find_cell_id.cpp:218-280): spacing and its constants
+    int spacing;
+    double cf_rmin, cf_growth, cf_inv_log_growth, cf_opt_const;
+    // the bodies of the last fcpt_set_bodies in polar coordinates (t_planet::get_r / get_phi)
+    double br[FCPT_MAX_BODIES], bphi[FCPT_MAX_BODIES];
+    double dt, indirect_x, indirect_y, frame_angle;
+};
+
 } // namespace fcpt
 
 #endif

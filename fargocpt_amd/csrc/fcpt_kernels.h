@@ -23,7 +23,7 @@ enum KernelId {
     KID_TRANSPORT_FUSED, KID_MASSFLOW, KID_CFL_RINGS, KID_THETA_GATED_BOUNDARY, KID_EXCHANGE_COPY,
     KID_DISK_ON_BODY, KID_VISC_FACTORS, KID_SOURCE_MARCH_ADI, KID_SOURCE_MARCH_ADI_WIDE,
     KID_ACCEL_ON_GAS, KID_SOURCE_MARCH_ADI_ACC, KID_TRANSPORT_RADIAL_MEANS, KID_CFL_RINGS_BC,
-    KID_DISK_ON_BODIES, KID_COUNT
+    KID_DISK_ON_BODIES, KID_PARTICLES, KID_COUNT
 };
 static_assert(KID_COUNT <= 64, "fcpt_profile_start selects kernels with a 64-bit mask");
 extern const char *const kKernelNames[KID_COUNT];
@@ -87,6 +87,7 @@ struct DiskBodies {
 };
 size_t disk_on_bodies_blocks(const Dev &P); // blocks of the first stage: `part` holds 4 * n * blocks doubles, `out` 4 * n
 void launch_disk_on_bodies(const Dev &P, int n, const DiskBodies &B, double *part, double *out, hipStream_t st);
+void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st);
 void launch_source_fused(const Dev &P, hipStream_t st);
 int launch_source_march(const Dev &P, hipStream_t st, bool fold_bc, bool *bc_folded, bool fold_cfl = false);
 void launch_cfl_final(const Dev &P, int apply_policy, hipStream_t st);

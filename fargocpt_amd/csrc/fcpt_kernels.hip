@@ -25,6 +25,7 @@ namespace fcpt {
 #include "kernels/transport.h"
 #include "kernels/transport_fused.h"
 #include "kernels/cfl.h"
+#include "kernels/particles.h"
 #include "kernels/launch.h"
 
 } // namespace fcpt

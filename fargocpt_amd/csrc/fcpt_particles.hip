@@ -1,0 +1,215 @@
+// Dust particles of the C ABI: device state, the launch of k_particles_step (kernels/particles.h) and the blocking
+// reads.  Replaces particles::integrate with ParticleIntegrator: midpoint (particles/particles.cpp:1525-1557,1579-1672)
+// for one radial slab; see include/fargocpt_hip.h for what is and is not covered.
+#include "fcpt_ctx.h"
+
+#include <cfloat>
+
+namespace fcpt {
+
+void particles_free(fcpt_ctx *c)
+{
+    if (c->part_block)
+        (void)hipFree(c->part_block);
+    c->part_block = nullptr;
+    c->part_id = nullptr;
+    c->part = ParticleArgs{};
+}
+
+} // namespace fcpt
+
+namespace {
+
+const char *const kGuardNames[9] = {"", "Ma < 1e-20", "Ma > 1e20", "CdE < 1e-20", "CdE > 1e20", "CdS < 1e-30",
+                                    "CdS > 1e30", "Cd < 1e-20",  "Cd > 1e20"};
+
+// waits for the queued steps; reports (once) a guard tripped since the last call
+int particles_wait(fcpt_ctx *c, const char *who)
+{
+    unsigned long long status = 0;
+    HIPCHK(hipMemcpyAsync(&status, c->part.status, sizeof(status), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (!status)
+        return FCPT_OK;
+    HIPCHK(hipMemsetAsync(c->part.status, 0, sizeof(status), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int guard = (int)(status & 0xffull);
+    const size_t slot = (size_t)(status >> 8);
+    unsigned long long id = 0;
+    if (slot < (size_t)c->part.n)
+        HIPCHK(hipMemcpy(&id, c->part_id + slot, sizeof(id), hipMemcpyDeviceToHost));
+    set_error("%s: particle id %llu tripped guard %d of calc_tstop (%s) and was left unchanged", who, id, guard,
+              guard >= 1 && guard <= 8 ? kGuardNames[guard] : "?");
+    return FCPT_EINVAL;
+}
+
+} // namespace
+
+extern "C" {
+
+int fcpt_particles_set(fcpt_ctx *c, const fcpt_particle_params *prm, int64_t n, const uint64_t *id, const double *r,
+                       const double *phi, const double *r_dot, const double *phi_dot, const double *radius,
+                       const double *stokes)
+{
+    if (!c || n < 0 || n > 0x7fffffff) {
+        set_error("fcpt_particles_set: null context or n outside 0 .. 2^31-1");
+        return FCPT_EINVAL;
+    }
+    if (n > 0 && (!prm || !id || !r || !phi || !r_dot || !phi_dot || !radius || !stokes)) {
+        set_error("fcpt_particles_set: null argument");
+        return FCPT_EINVAL;
+    }
+    if (n > 0 && c->d.nranks != 1) {
+        set_error("fcpt_particles_set: particles need the whole grid in one slab (this context is slab %d of %d)", c->d.rank,
+                  c->d.nranks);
+        return FCPT_EINVAL;
+    }
+    if (n > 0 && (!(prm->escape_radius_min >= c->d.rmin) || !(prm->escape_radius_max <= c->d.rmax) ||
+                  !(prm->escape_radius_min < prm->escape_radius_max))) {
+        set_error("fcpt_particles_set: escape radii [%g, %g] must be ordered and inside the grid [%g, %g]", prm->escape_radius_min,
+                  prm->escape_radius_max, c->d.rmin, c->d.rmax);
+        return FCPT_EINVAL;
+    }
+    HIPCHK(hipStreamSynchronize(c->stream)); // a queued step may still use the arrays
+    particles_free(c);
+    if (n == 0)
+        return FCPT_OK;
+    // one block: status word, ids, six double arrays, alive bytes
+    const size_t nn = (size_t)n;
+    const size_t bytes = 8 + nn * 8 * 7 + nn;
+    void *block = nullptr;
+    if (hipMalloc(&block, bytes) != hipSuccess) {
+        set_error("hipMalloc(%zu bytes) for the particles failed", bytes);
+        return FCPT_ENOMEM;
+    }
+    c->part_block = block;
+    char *p = (char *)block;
+    ParticleArgs &A = c->part;
+    A.status = (unsigned long long *)p;
+    c->part_id = (unsigned long long *)(p + 8);
+    double *arr = (double *)(p + 8 + nn * 8);
+    A.r = arr;
+    A.phi = arr + nn;
+    A.r_dot = arr + 2 * nn;
+    A.phi_dot = arr + 3 * nn;
+    A.stokes = arr + 4 * nn;
+    A.radius = arr + 5 * nn;
+    A.alive = (unsigned char *)(arr + 6 * nn);
+    const double *src[6] = {r, phi, r_dot, phi_dot, stokes, radius};
+    int rc = FCPT_OK;
+    auto chk = [&](hipError_t e) {
+        if (e != hipSuccess && rc == FCPT_OK) {
+            set_error("fcpt_particles_set: copy to the device failed: %s", hipGetErrorString(e));
+            rc = FCPT_EHIP;
+        }
+    };
+    chk(hipMemsetAsync(A.status, 0, 8, c->stream));
+    chk(hipMemcpyAsync(c->part_id, id, nn * 8, hipMemcpyHostToDevice, c->stream));
+    for (int k = 0; k < 6; ++k)
+        chk(hipMemcpyAsync(arr + k * nn, src[k], nn * 8, hipMemcpyHostToDevice, c->stream));
+    chk(hipMemsetAsync(A.alive, 1, nn, c->stream));
+    chk(hipStreamSynchronize(c->stream));
+    if (rc) {
+        particles_free(c);
+        return rc;
+    }
+    A.n = (int)n;
+    A.particle_density = prm->particle_density;
+    A.molecule_mass = prm->molecule_mass;
+    A.molecule_radius = prm->molecule_radius;
+    A.k_B = prm->k_B;
+    // parameters.cpp:957-961
+    A.escape_max_sq = prm->escape_radius_max * prm->escape_radius_max - DBL_EPSILON;
+    A.escape_min_sq = prm->escape_radius_min * prm->escape_radius_min + DBL_EPSILON;
+    A.gravity_cartesian = prm->gravity_cartesian != 0;
+    A.spacing = c->d.radial_spacing;
+    A.cf_rmin = c->d.rmin;
+    A.cf_growth = c->geo.cf_growth;
+    A.cf_inv_log_growth = c->geo.cf_inv_log_growth;
+    A.cf_opt_const = c->geo.cf_opt_const;
+    return FCPT_OK;
+}
+
+int fcpt_particles_step(fcpt_ctx *c, double dt, double indirect_x, double indirect_y, double frame_angle)
+{
+    if (!c)
+        return FCPT_EINVAL;
+    if (c->part.n <= 0)
+        return FCPT_OK;
+    join_side(c);
+    ProfScope prof_scope(c);
+    ParticleArgs A = c->part;
+    const Dev &P = c->P;
+    for (int k = 0; k < P.nbodies; ++k) { // t_planet::get_r / get_phi
+        A.br[k] = std::sqrt(P.bx[k] * P.bx[k] + P.by[k] * P.by[k]);
+        A.bphi[k] = std::atan2(P.by[k], P.bx[k]);
+    }
+    A.dt = dt;
+    A.indirect_x = indirect_x;
+    A.indirect_y = indirect_y;
+    A.frame_angle = frame_angle;
+    launch_particles(P, A, c->stream);
+    HIPCHK(hipGetLastError());
+    return FCPT_OK;
+}
+
+int fcpt_particles_count(fcpt_ctx *c, int64_t *n_alive)
+{
+    if (!c || !n_alive)
+        return FCPT_EINVAL;
+    *n_alive = 0;
+    if (c->part.n <= 0)
+        return FCPT_OK;
+    if (int rc = particles_wait(c, "fcpt_particles_count"))
+        return rc;
+    std::vector<unsigned char> alive((size_t)c->part.n);
+    HIPCHK(hipMemcpy(alive.data(), c->part.alive, alive.size(), hipMemcpyDeviceToHost));
+    int64_t m = 0;
+    for (unsigned char a : alive)
+        m += a != 0;
+    *n_alive = m;
+    return FCPT_OK;
+}
+
+int fcpt_particles_get(fcpt_ctx *c, int64_t capacity, uint64_t *id, double *r, double *phi, double *r_dot, double *phi_dot,
+                       double *radius, double *stokes, int64_t *n)
+{
+    if (!c || !n || capacity < 0)
+        return FCPT_EINVAL;
+    *n = 0;
+    if (c->part.n <= 0)
+        return FCPT_OK;
+    if (int rc = particles_wait(c, "fcpt_particles_get"))
+        return rc;
+    const size_t nn = (size_t)c->part.n;
+    std::vector<unsigned char> alive(nn);
+    std::vector<double> host(6 * nn);
+    std::vector<unsigned long long> ids(id ? nn : 0);
+    if (id)
+        HIPCHK(hipMemcpy(ids.data(), c->part_id, nn * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(alive.data(), c->part.alive, nn, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(host.data(), c->part.r, 6 * nn * sizeof(double), hipMemcpyDeviceToHost)); // r is the first of six arrays
+    int64_t m = 0;
+    for (unsigned char a : alive)
+        m += a != 0;
+    *n = m;
+    if (m > capacity) {
+        set_error("fcpt_particles_get: %lld live particles, room for %lld", (long long)m, (long long)capacity);
+        return FCPT_EINVAL;
+    }
+    double *out[6] = {r, phi, r_dot, phi_dot, stokes, radius}; // the order of the device block
+    size_t k = 0;
+    for (size_t s = 0; s < nn; ++s) { // compaction on download: ascending slot order
+        if (!alive[s])
+            continue;
+        if (id)
+            id[k] = ids[s];
+        for (int q = 0; q < 6; ++q)
+            if (out[q])
+                out[q][k] = host[q * nn + s];
+        ++k;
+    }
+    return FCPT_OK;
+}
+
+} // extern "C"

@@ -20,10 +20,13 @@
 // for the default unit system (l0 = 1 au, m0 = 1 solMass).  A key the reference's reader does not know is
 // fatal, as in the reference (src/config.cpp:134-138: a typo must not silently change the physics); --lenient
 // downgrades that to a warning.  Keys the reference knows but the gas path does not consume are accepted (listed
-// unless -q); features outside the path that a setup switches on (self-gravity, particles, FLD ...) are refused.
+// unless -q); features outside the path that a setup switches on (self-gravity, FLD ...) are refused.
+// IntegrateParticles: dust particles with gas drag (fcpt_particles_*): Particle* keys, placement, one particle step per
+// hydro step, Disk: No, snapshots/<n>/particles.dat and restart from it; see DESIGN.md section 4.
 #include "../../../include/fargocpt_hip.h"
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -181,7 +184,7 @@ const char *const kReferenceKeys[] = {
     "writevelocity", "writeverticalopticaldepth", "writeviscosity", "writevisibility",};
 // Features of the reference outside the gas path of this driver: a setup that switches one on is refused, not run
 // without it (out of scope).
-const char *const kRefusedWhenOn[] = {"selfgravity", "integrateparticles", "radiativediffusion", "rochelobeoverflow",
+const char *const kRefusedWhenOn[] = {"selfgravity", "radiativediffusion", "rochelobeoverflow",
                                       "keepdiskmassconstant", "circumbinaryring", "planetorbitdisktest",
                                       "viscaccretmassflowtest"};
 
@@ -194,7 +197,7 @@ double TEMP0 = G_CGS * MU / KB * M0 / L0;
 double TIME0 = std::sqrt(L0 * L0 * L0 / (G_CGS * M0));
 
 // "<number> [unit]" -> code units for the quantity kind
-enum Kind { K_NONE, K_LEN, K_MASS, K_SIGMA, K_TEMP, K_VISC };
+enum Kind { K_NONE, K_LEN, K_MASS, K_SIGMA, K_TEMP, K_VISC, K_DENS };
 double number(const std::string &s, Kind kind)
 {
     std::istringstream is(s);
@@ -210,6 +213,8 @@ double number(const std::string &s, Kind kind)
             return v * AU_CM / L0;
         if (u == "cm")
             return v / L0;
+        if (u == "m")
+            return v * 100.0 / L0;
         if (u == "solradius")
             return v * 6.957e10 / L0;
     } else if (kind == K_MASS) {
@@ -228,6 +233,9 @@ double number(const std::string &s, Kind kind)
     } else if (kind == K_VISC) {
         if (u == "cm2/s")
             return v / (L0 * L0 / TIME0);
+    } else if (kind == K_DENS) {
+        if (u == "g/cm3")
+            return v / (M0 / (L0 * L0 * L0));
     }
     fprintf(stderr, "fargocpt_hip: unit '%s' in '%s' not understood\n", u.c_str(), s.c_str());
     exit(2);
@@ -453,6 +461,33 @@ void config_to_desc(const Config &c, fcpt_desc &d)
     if (!c.nbody.empty() && c.nbody[0].count("mass"))
         d.hydro_center_mass = number(c.nbody[0].at("mass"), K_MASS);
 }
+
+// Dust particles: the Particle* keys of parameters.cpp:853-961 with their units and defaults
+struct ParticleSetup {
+    bool on = false, cartesian_gravity = false;
+    long n = 0;
+    int species = 1;
+    double radius = 0, radius_factor = 10, eccentricity = 0, density = 0, slope = 0;
+    double rmin = 0, rmax = 0, escape_min = 0, escape_max = 0;
+};
+// one record of snapshots/<n>/particles.dat: t_particle (particles/particle.h), 96 bytes
+struct ParticleRecord {
+    uint64_t id;
+    double r, phi, r_dot, phi_dot, r_ddot, phi_ddot, mass, radius, timestep, facold, stokes;
+};
+static_assert(sizeof(ParticleRecord) == 96, "the reference's particle record");
+// the driver's own generator for the initial placement (splitmix64; the reference's random stream is not reproduced)
+struct Random {
+    uint64_t state;
+    double uniform() // [0, 1)
+    {
+        uint64_t z = (state += 0x9e3779b97f4a7c15ull);
+        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+        z ^= z >> 31;
+        return (double)(z >> 11) * (1.0 / 9007199254740992.0);
+    }
+};
 
 struct Body {
     double a, m, phase, rsm_factor;
@@ -740,6 +775,47 @@ int main(int argc, char **argv)
                 return 2;
             }
     }
+    // IntegrateParticles: the Particle* keys (parameters.cpp:853-961); what the particle step of the library does not
+    // cover is refused here, each with the key that asks for it, before any device is asked for
+    ParticleSetup ps;
+    ps.on = cfg.flag("IntegrateParticles", false);
+    const bool calculate_disk = !ps.on || cfg.flag("Disk", true); // parameters::calculate_disk; without particles as before
+    if (ps.on) {
+        auto refuse = [](const char *what) {
+            fprintf(stderr, "fargocpt_hip: %s is not supported with IntegrateParticles\n", what);
+            return 2;
+        };
+        if (std::tolower(cfg.str("ParticleIntegrator", "m")[0]) != 'm')
+            return refuse("ParticleIntegrator other than midpoint (the explicit adaptive integrator)");
+        if (!cfg.flag("ParticleGasDragEnabled", true))
+            return refuse("ParticleGasDragEnabled: no");
+        if (cfg.flag("ParticleDustDiffusion", false))
+            return refuse("ParticleDustDiffusion");
+        if (cfg.flag("ParticleDiskGravityEnabled", false))
+            return refuse("ParticleDiskGravityEnabled");
+        if (lower(cfg.str("ParticleSurfaceDensitySlope", "SigmaSlope")) == "gas")
+            return refuse("ParticleSurfaceDensitySlope: gas");
+        if (d.integrator != FCPT_INTEGRATOR_EULER)
+            return refuse("Integrator: Leapfrog");
+        if (want_ranks > 1 || slab.nranks > 1)
+            return refuse("--ranks > 1 (particles need the whole grid in one slab)");
+        ps.cartesian_gravity = cfg.flag("CartesianParticles", false); // with the midpoint integrator: the form of the gravity only (parameters.cpp:927-932)
+        ps.n = (long)num(cfg, "NumberOfParticles", 0);
+        ps.radius = num(cfg, "ParticleRadius", 100.0 / L0, K_LEN);
+        ps.species = std::max(1, (int)num(cfg, "ParticleSpeciesNumber", 1));
+        ps.radius_factor = num(cfg, "ParticleRadiusIncreaseFactor", 10.0);
+        ps.eccentricity = num(cfg, "ParticleEccentricity", 0.0);
+        ps.density = num(cfg, "ParticleDensity", 2.65 / (M0 / (L0 * L0 * L0)), K_DENS);
+        {
+            const std::string sl = cfg.str("ParticleSurfaceDensitySlope", "SigmaSlope");
+            const double slope = lower(sl) == "sigmaslope" ? d.sigma_slope : number(sl, K_NONE);
+            ps.slope = -slope + 1.0; // r^-slope like the gas, and a factor r for the ring (parameters.cpp:875-883)
+        }
+        ps.rmin = num(cfg, "ParticleMinimumRadius", d.rmin, K_LEN);
+        ps.rmax = num(cfg, "ParticleMaximumRadius", d.rmax, K_LEN);
+        ps.escape_min = std::max(num(cfg, "ParticleMinimumEscapeRadius", d.rmin, K_LEN), d.rmin); // clamped to the grid (:943-955)
+        ps.escape_max = std::min(num(cfg, "ParticleMaximumEscapeRadius", d.rmax, K_LEN), d.rmax);
+    }
     // --bodies free: the bodies move under their own gravity (fcpt_nbody_*) and, with DiskFeedback, under the disk's;
     // what that mode does not cover is refused here, before any device is asked for
     const bool free_bodies = bodies_mode == "free";
@@ -922,6 +998,7 @@ int main(int argc, char **argv)
     // (ComputeIndirectTermNbody, frame_of_reference.cpp:138-160) -- for circular orbits the time average of
     // G m r_p / a^3 over [t, t + dt], in closed form.
     const bool indirect = lower(cfg.str("HydroFrameCenter", "primary")) == "primary";
+    double step_itx = 0.0, step_ity = 0.0; // the indirect term of the step being set up: the particles feel it too
     auto set_bodies = [&](double t, double dt) {
         double x[FCPT_MAX_BODIES], y[FCPT_MAX_BODIES], m[FCPT_MAX_BODIES], rsm[FCPT_MAX_BODIES];
         const int n = (int)std::min<size_t>(bodies.size(), FCPT_MAX_BODIES);
@@ -949,6 +1026,8 @@ int main(int argc, char **argv)
             }
         }
         CHECK(fcpt_set_bodies(ctx, n, x, y, m, rsm, itx, ity));
+        step_itx = itx;
+        step_ity = ity;
     };
     // ---- --bodies free: the bodies as a system of their own (fcpt_nbody_*), every rank its own bit-identical copy --------
     fcpt_nbody *nb = nullptr;
@@ -1035,6 +1114,8 @@ int main(int argc, char **argv)
             rsm[k] = b.a * std::cbrt(b.m / (3.0 * d.hydro_center_mass)) * b.rsm_factor;
         }
         CHECK(fcpt_set_bodies(ctx, nfree, x, y, m, rsm, itx, ity));
+        step_itx = itx;
+        step_ity = ity;
         if (dt > 0.0) { // apply_indirect_term_on_Nbody
             double kx[FCPT_MAX_BODIES], ky[FCPT_MAX_BODIES];
             for (int k = 0; k < nfree; ++k) {
@@ -1113,6 +1194,94 @@ int main(int argc, char **argv)
             CHECK(fcpt_set_body_irradiation(ctx, n, temp, rad, ramp));
     }
     CHECK(fcpt_init_physics(ctx));
+
+    // ---- dust particles: init_dust_profile / insert_particle (particles/particles.cpp:426-475,477-520) ------------------
+    // mass, initial speed (r_ddot) and eccentricity (phi_ddot) of the record never change: kept here by id
+    std::map<uint64_t, std::array<double, 3>> particle_fixed;
+    fcpt_particle_params pprm;
+    CHECK(fcpt_particle_params_default(&d, &pprm));
+    auto upload_particles = [&](const std::vector<ParticleRecord> &rec) {
+        const size_t n = rec.size();
+        std::vector<uint64_t> id(n);
+        std::vector<double> a[6];
+        for (auto &v : a)
+            v.resize(n);
+        particle_fixed.clear();
+        for (size_t k = 0; k < n; ++k) {
+            id[k] = rec[k].id;
+            a[0][k] = rec[k].r, a[1][k] = rec[k].phi, a[2][k] = rec[k].r_dot, a[3][k] = rec[k].phi_dot;
+            a[4][k] = rec[k].radius, a[5][k] = rec[k].stokes;
+            particle_fixed[rec[k].id] = {rec[k].mass, rec[k].r_ddot, rec[k].phi_ddot};
+        }
+        CHECK(fcpt_particles_set(ctx, &pprm, (int64_t)n, id.data(), a[0].data(), a[1].data(), a[2].data(), a[3].data(), a[4].data(),
+                                 a[5].data()));
+    };
+    auto download_particles = [&]() {
+        int64_t n = 0;
+        CHECK(fcpt_particles_count(ctx, &n));
+        std::vector<uint64_t> id((size_t)n);
+        std::vector<double> a[6];
+        for (auto &v : a)
+            v.resize((size_t)n);
+        CHECK(fcpt_particles_get(ctx, n, id.data(), a[0].data(), a[1].data(), a[2].data(), a[3].data(), a[4].data(), a[5].data(), &n));
+        std::vector<ParticleRecord> rec((size_t)n);
+        for (size_t k = 0; k < (size_t)n; ++k) {
+            const std::array<double, 3> &fx = particle_fixed[id[k]];
+            rec[k] = ParticleRecord{id[k], a[0][k], a[1][k], a[2][k], a[3][k], fx[1], fx[2], fx[0], a[4][k], 0.0, 0.0, a[5][k]};
+        }
+        return rec;
+    };
+    if (ps.on) {
+        pprm.particle_density = ps.density;
+        pprm.molecule_mass = d.mu * MU / M0;
+        pprm.molecule_radius = 1.5e-8 / L0;
+        pprm.k_B = KB / ((M0 * L0 * L0 / (TIME0 * TIME0)) / TEMP0);
+        pprm.escape_radius_min = ps.escape_min;
+        pprm.escape_radius_max = ps.escape_max;
+        pprm.gravity_cartesian = ps.cartesian_gravity ? 1 : 0;
+    }
+    if (ps.on && !restarting) {
+        // power_law_distribution (:55-82): keep eccentric orbits inside the particle bounds
+        double rmin = ps.rmin, rmax = ps.rmax;
+        if (d.rmax < ps.rmax * (1.0 + ps.eccentricity))
+            rmax = ps.rmax / (1.0 + ps.eccentricity);
+        if (d.rmin > ps.rmin * (1.0 - ps.eccentricity))
+            rmin = ps.rmin / (1.0 - ps.eccentricity);
+        Random rnd{20240611ull};
+        std::vector<ParticleRecord> rec((size_t)ps.n);
+        for (long i = 0; i < ps.n; ++i) {
+            const double x = rnd.uniform(), n1 = ps.slope + 1.0;
+            const double a = ps.slope == -1.0 ? std::exp(std::log(rmax / rmin) * x) * rmin
+                                              : std::exp(std::log(x * (-std::pow(rmin, n1) + std::pow(rmax, n1)) + std::pow(rmin, n1)) / n1);
+            const double phi = 2.0 * M_PI * rnd.uniform();
+            const double e = ps.eccentricity * rnd.uniform();
+            ParticleRecord &q = rec[(size_t)i];
+            memset(&q, 0, sizeof(q));
+            q.id = (uint64_t)i;
+            q.radius = ps.radius * std::pow(ps.radius_factor, (double)(i % ps.species));
+            q.mass = 4.0 / 3.0 * M_PI * std::pow(q.radius, 3) * ps.density;
+            const double r = a * (1.0 + e);
+            const double v = std::sqrt(d.G * (d.hydro_center_mass + q.mass) / a) * std::sqrt((1.0 - e) / (1.0 + e));
+            q.r = r;
+            q.phi = phi;
+            q.r_dot = 0.0;
+            q.phi_dot = v / r;
+            q.r_ddot = v;
+            q.phi_ddot = e;
+            q.stokes = 1.0;
+        }
+        // check_tstop (:1277-1311): the Stokes number of every particle where and as it starts.  A step of length zero of
+        // the library's kernel evaluates exactly that -- the drag law at (r, phi) with the particle's own velocity -- and
+        // moves nothing; its Stokes numbers go into the initial state.
+        upload_particles(rec);
+        CHECK(fcpt_particles_step(ctx, 0.0, 0.0, 0.0, 0.0));
+        std::map<uint64_t, double> st;
+        for (const ParticleRecord &q : download_particles())
+            st[q.id] = q.stokes;
+        for (ParticleRecord &q : rec)
+            q.stokes = st.count(q.id) ? st[q.id] : 0.0;
+        upload_particles(rec);
+    }
 
     // ---- output files -------------------------------------------------------------------------
     if (slab.master()) {
@@ -1269,6 +1438,15 @@ int main(int argc, char **argv)
             }
             fclose(bf);
         }
+        if (ps.on && !name) { // particles::write (particles.cpp:2270-2330): the live particles, one record each
+            const std::vector<ParticleRecord> rec = download_particles();
+            FILE *pf = fopen((dir + "particles.dat").c_str(), "wb");
+            if (!pf || fwrite(rec.data(), sizeof(ParticleRecord), rec.size(), pf) != rec.size()) {
+                fprintf(stderr, "fargocpt_hip: cannot write %sparticles.dat\n", dir.c_str());
+                exit(1);
+            }
+            fclose(pf);
+        }
         misc_entry misc;
         memset(&misc, 0, sizeof(misc));
         misc.timestep = nsnap;
@@ -1374,6 +1552,19 @@ int main(int argc, char **argv)
             set_bodies(time, 0.0);
         }
         CHECK(fcpt_recalculate_derived(ctx));
+        if (ps.on) { // particles::restart (particles.cpp:790-890)
+            FILE *pf = fopen((restart_dir + "particles.dat").c_str(), "rb");
+            std::vector<ParticleRecord> rec;
+            ParticleRecord q;
+            while (pf && fread(&q, sizeof(q), 1, pf) == 1)
+                rec.push_back(q);
+            if (!pf) {
+                fprintf(stderr, "fargocpt_hip: cannot read %sparticles.dat\n", restart_dir.c_str());
+                return 1;
+            }
+            fclose(pf);
+            upload_particles(rec);
+        }
         if (!quiet)
             printf("Restarting from %s at time %f (snapshot %u, monitor step %u).\n", restart_dir.c_str(), time,
                    misc.timestep, misc.nTimeStep);
@@ -1415,7 +1606,7 @@ int main(int argc, char **argv)
     double sum_dt = 0, min_dt = 1e300, max_dt = 0;
     const auto t_start = std::chrono::steady_clock::now();
     auto t_last = t_start;
-    const bool moving = bodies.size() > 1 || free_bodies;
+    const bool moving = bodies.size() > 1 || free_bodies || ps.on; // (particles are stepped by the host-stepped loop)
     if (free_bodies && !restarting) {
         write_nbody_rows(0, 0, 0.0, true);
     }
@@ -1473,11 +1664,22 @@ int main(int argc, char **argv)
         } else if (moving) {
             set_bodies(time, step_dt);
         }
-        CHECK(fcpt_step(ctx, step_dt));
+        if (ps.on) // simulation.cpp:177-180 and the particles' part of handle_corotation (:184)
+            CHECK(fcpt_particles_step(ctx, step_dt, step_itx, step_ity, d.omega_frame * step_dt));
+        if (calculate_disk)
+            CHECK(fcpt_step(ctx, step_dt));
         if (free_bodies)
             advance_bodies(step_dt); // on the host, under the step's kernels
-        exchange(); // simulation.cpp:236
-        CHECK(fcpt_post(ctx, step_dt));
+        if (calculate_disk) {
+            exchange(); // simulation.cpp:236
+            CHECK(fcpt_post(ctx, step_dt));
+        } else { // Disk: No -- the gas is frozen, the clock runs (simulation.cpp:226-227)
+            fcpt_clock clk;
+            CHECK(fcpt_get_clock(ctx, &clk));
+            clk.time += step_dt;
+            clk.n_hydro_iter += 1;
+            CHECK(fcpt_set_clock(ctx, &clk));
+        }
         time += step_dt;
         ++n_iter;
         sum_dt += step_dt;

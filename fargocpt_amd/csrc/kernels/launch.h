@@ -13,7 +13,7 @@ const char *const kKernelNames[KID_COUNT] = {
     "k_transport_theta_march", "k_transport_fused", "k_massflow", "k_cfl_rings", "k_theta_march_gated_boundary",
     "k_exchange_copy", "k_disk_on_body", "k_visc_factors", "k_source_march_adi", "k_source_march_adi_wide",
     "k_accel_on_gas", "k_source_march_adi_acc",
-    "k_transport_radial_means", "k_cfl_rings_bc", "k_disk_on_bodies"};
+    "k_transport_radial_means", "k_cfl_rings_bc", "k_disk_on_bodies", "k_particles_step"};
 
 thread_local Profiler *g_prof = nullptr;
 
@@ -531,6 +531,15 @@ void launch_disk_on_bodies(const Dev &P, int n, const DiskBodies &B, double *par
     static_assert(FCPT_MAX_BODIES == 8, "one instance of k_disk_on_bodies per body count");
     with_value<1, 2, 3, 4, 5, 6, 7, 8>(n, [&](auto N) { KLAUNCH(KID_DISK_ON_BODIES, k_disk_on_bodies<TARG(N)>, grid, block, P, B, need_h, part); });
     KLAUNCH(KID_DISK_ON_BODIES, k_disk_on_bodies_final, dim3(n), dim3(256), (const double *)part, (int)(grid.x * grid.y), out);
+}
+
+// one lane per particle slot (dead slots return at once); the view's state grids are those of the start of the step
+void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st)
+{
+    if (A.n <= 0)
+        return;
+    const dim3 grid((A.n + 255) / 256), block(256);
+    with_bool(P.adiabatic, [&](auto ADI) { KLAUNCH(KID_PARTICLES, k_particles_step<TARG(ADI)>, grid, block, P, A); });
 }
 
 // rings whose CFL terms read nothing the ghost exchange or the boundary kernels write: ring i reads rows i

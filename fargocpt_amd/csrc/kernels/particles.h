@@ -1,0 +1,271 @@
+// Part of fcpt_kernels.hip (one translation unit, namespace fcpt): Lagrangian dust particles with gas drag.
+// Not a stand-alone header: included once, in the order given there.
+//
+// k_particles_step restates, per particle and statement by statement (paths relative to the reference's src/):
+//   update_velocities_from_indirect_term  particles/particles.cpp:1326-1341  (polar form)
+//   integrate_exponential_midpoint        particles/particles.cpp:1579-1672  (Zhu et al. 2014, Mignone et al. 2019)
+//     calculate_gas_drag_expmid :1247-1273, interpolate_quantities :1216-1244, find_nearest :115-133,
+//     interpolate_bilinear :1062-1127, calc_tstop :1130-1214, calculate_dust_smoothing :896-912,
+//     calculate_derivitives_from_star_and_planets(_in_cart) :981-1060
+//   the escape test of move()             particles/particles.cpp:2019-2031
+//   rotate                                particles/particles.cpp:2394-2395
+//
+// Shape: one lane per live particle, structure-of-arrays state, no atomics, no LDS, no waits between workgroups.
+// The ring and column of a particle differ from lane to lane, so the per-ring arrays are read through plain vector
+// loads here (the ROWU / readfirstlane promotion of the grid kernels does not apply), and the gathers from the
+// phi-contiguous grids are element-granular: what keeps them cheap is the order of the particles, which the kernel
+// does not choose (fcpt_particles_set keeps the caller's order).  Bodies and scalars arrive as kernel arguments.
+//
+// rho = Sigma / (density_factor H) and T are formed in registers at the corners of the interpolation cell from
+// Sigma (and e for the ideal EOS) with the expressions of k_iso_cs_h / k_temperature / k_adi_derived; no RHO or
+// TEMPERATURE grid is read.
+//
+// DEPARTURE from the reference: for a particle beyond Rmed[Nr-1] the reference reads row Nr of a scalar grid, which
+// is out of bounds.  Here the lower row of the b grid (cell centres) is clamped to [0, Nr-2] -- linear extrapolation
+// from the last two rows, the mirror of what the reference's release build does below Rmed[0] -- and the lower row
+// of the a grid (interfaces) to [0, Nr-1].
+
+// particles.cpp:84-95
+__device__ __forceinline__ double particle_check_angle(double phi)
+{
+    if (phi >= 2.0 * M_PI)
+        return phi - 2.0 * M_PI;
+    if (phi < 0.0)
+        return phi + 2.0 * M_PI;
+    return phi;
+}
+
+// Largest i in [0, nr-1] with Rinf[i] <= r (get_rinf_id with the release build's clamp).  The closed form of the
+// spacing gives the guess; where it is off (rounding at an interface, a radii array of the caller's own) a binary
+// search over the context's array decides, so the result is right for any monotonic grid.
+__device__ __forceinline__ int particle_rinf_id(const double *Rinf, int nr, const ParticleArgs &A, double r)
+{
+    double did;
+    if (A.spacing == FCPT_SPACING_LOGARITHMIC)
+        did = log(r / A.cf_rmin) * A.cf_inv_log_growth;
+    else if (A.spacing == FCPT_SPACING_ARITHMETIC)
+        did = (r - A.cf_rmin) * A.cf_growth;
+    else
+        did = log((r - A.cf_rmin) * A.cf_opt_const + 1.0) * A.cf_inv_log_growth;
+    int g = (int)floor(dmin(dmax(did, -1.0), (double)nr)) + 1;
+    g = g < 0 ? 0 : (g > nr - 1 ? nr - 1 : g);
+    if (Rinf[g] <= r && (g == nr - 1 || r < Rinf[g + 1]))
+        return g;
+    int lo = 0, hi = nr - 1; // invariant: the answer is in [lo, hi]
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (Rinf[mid] <= r)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    return lo;
+}
+
+// Sigma, T and H of cell (i, j) as the derived-quantity kernels form them
+struct ParticleGas {
+    double rho, T;
+};
+template <bool ADI> __device__ __forceinline__ double particle_scale_height(const Dev &P, int i, int j)
+{
+    if (!ADI)
+        return P.cs_ring.p[i] * P.g_inv_omk.p[i];
+    const double cs = sqrt(P.gamma * (P.gamma - 1.0) * P.energy[IDX(i, j)] / P.sigma[IDX(i, j)]);
+    return cs / sqrt(P.gamma) * P.g_inv_omk.p[i];
+}
+template <bool ADI> __device__ __forceinline__ ParticleGas particle_gas(const Dev &P, int i, int j)
+{
+    const double sg = P.sigma[IDX(i, j)];
+    ParticleGas g;
+    if (ADI) {
+        const double e = P.energy[IDX(i, j)];
+        const double cs = sqrt(P.gamma * (P.gamma - 1.0) * e / sg);
+        const double H = cs / sqrt(P.gamma) * P.g_inv_omk.p[i];
+        g.T = P.mu / P.Rgas * (P.gamma - 1.0) * e / sg;
+        g.rho = sg / (P.density_factor * H);
+    } else {
+        const double cs = P.cs_ring.p[i];
+        g.T = P.mu / P.Rgas * (cs * cs);
+        g.rho = sg / (P.density_factor * (cs * P.g_inv_omk.p[i]));
+    }
+    return g;
+}
+// particles.cpp:1116-1124
+__device__ __forceinline__ double particle_bilinear(double Qmm, double Qpm, double Qmp, double Qpp, double rm, double rp, double phim,
+                                                    double phip, double dphi, double r, double phi)
+{
+    const double Qm = ((phip - phi) * Qmm + (phi - phim) * Qmp) / dphi;
+    const double Qp = ((phip - phi) * Qpm + (phi - phim) * Qpp) / dphi;
+    return ((rp - r) * Qm + (r - rm) * Qp) / (rp - rm);
+}
+
+template <bool ADI> __global__ void __launch_bounds__(256) k_particles_step(const Dev P, const ParticleArgs A)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= A.n || !A.alive[n])
+        return;
+    const double dt = A.dt;
+    const double r0 = A.r[n], phi0 = A.phi[n], radius = A.radius[n], stokes_old = A.stokes[n];
+    double r_dot0, phi_dot0;
+    { // update_velocities_from_indirect_term
+        double s, c;
+        sincos(phi0, &s, &c);
+        r_dot0 = A.r_dot[n] + dt * (A.indirect_x * c + A.indirect_y * s);
+        phi_dot0 = A.phi_dot[n] + dt * (-A.indirect_x * s + A.indirect_y * c) / r0;
+    }
+    const double l0 = r0 * r0 * phi_dot0;
+    const double hfdt = 0.5 * dt;
+    // half drift
+    const double r1 = r0 + r_dot0 * hfdt;
+    const double phi1 = particle_check_angle(phi0 + 0.5 * (l0 / (r0 * r0) + l0 / (r1 * r1)) * hfdt);
+
+    // ---- gas at (r_tmp, phi1): find_nearest + four bilinear interpolations ------------------------------------
+    const int nr = P.nr, nphi = P.nphi;
+    const double *Rinf = P.Rinf.p, *Rmed = P.Rmed.p;
+    const double r_tmp = fmin(fmax(r1, Rinf[0]), Rinf[nr]); // Rsup[nr-1] = Rinf[nr]
+    const int ia = particle_rinf_id(Rinf, nr, A, r_tmp);
+    const int ib_raw = r_tmp >= Rmed[ia] ? ia : ia - 1; // Rinf[ia] < Rmed[ia] < Rinf[ia+1]
+    const int ib = ib_raw < 0 ? 0 : (ib_raw > nr - 2 ? nr - 2 : ib_raw);
+    // (phi1 is in [0, 2 pi]: where the product rounds up to nphi the particle still belongs to the last column)
+    int ja = (int)floor(phi1 * P.invdphi);
+    ja = ja < 0 ? 0 : (ja > nphi - 1 ? nphi - 1 : ja);
+    const int jap = ja == nphi - 1 ? 0 : ja + 1;
+    int jb = (int)floor((phi1 - 0.5 * P.dphi) * P.invdphi) % nphi;
+    jb = jb < 0 ? jb + nphi : jb;
+    const int jbp = jb == nphi - 1 ? 0 : jb + 1;
+    // cell-centred columns: the three cases at the seam (particles.cpp:1096-1113)
+    double phim_b, phip_b;
+    if (jb == nphi - 1) {
+        if (phi1 < M_PI) {
+            phim_b = -0.5 * P.dphi;
+            phip_b = 0.5 * P.dphi;
+        } else {
+            phim_b = (jb + 0.5) * P.dphi;
+            phip_b = (jb + 1.5) * P.dphi;
+        }
+    } else {
+        phim_b = (jb + 0.5) * P.dphi;
+        phip_b = (jbp + 0.5) * P.dphi;
+    }
+    const double phim_a = ja * P.dphi, phip_a = (double)(ja + 1) * P.dphi; // :1085-1094
+    const double rbm = Rmed[ib], rbp = Rmed[ib + 1], ram = Rinf[ia], rap = Rinf[ia + 1];
+
+    const ParticleGas gmm = particle_gas<ADI>(P, ib, jb), gpm = particle_gas<ADI>(P, ib + 1, jb);
+    const ParticleGas gmp = particle_gas<ADI>(P, ib, jbp), gpp = particle_gas<ADI>(P, ib + 1, jbp);
+    const double rho = particle_bilinear(gmm.rho, gpm.rho, gmp.rho, gpp.rho, rbm, rbp, phim_b, phip_b, P.dphi, r_tmp, phi1);
+    const double temperature = particle_bilinear(gmm.T, gpm.T, gmp.T, gpp.T, rbm, rbp, phim_b, phip_b, P.dphi, r_tmp, phi1);
+    const double vg_radial = particle_bilinear(P.vrad[IDX(ia, jb)], P.vrad[IDX(ia + 1, jb)], P.vrad[IDX(ia, jbp)], P.vrad[IDX(ia + 1, jbp)],
+                                               ram, rap, phim_b, phip_b, P.dphi, r_tmp, phi1);
+    const double vg_azimuthal = particle_bilinear(P.vazi[IDX(ib, ja)], P.vazi[IDX(ib + 1, ja)], P.vazi[IDX(ib, jap)], P.vazi[IDX(ib + 1, jap)],
+                                                  rbm, rbp, phim_a, phip_a, P.dphi, r_tmp, phi1) +
+                                r_tmp * P.omega_frame;
+
+    // calculate_gas_drag_expmid
+    const double minus_r_dotel_r = vg_radial - r_dot0;
+    const double minus_l_rel = r1 * vg_azimuthal - l0;
+    const double vrel_phi = vg_azimuthal - phi_dot0 * r0;
+    const double vrel = sqrt(minus_r_dotel_r * minus_r_dotel_r + vrel_phi * vrel_phi);
+
+    // ---- calc_tstop --------------------------------------------------------------------------------------------
+    const double m0 = A.molecule_mass, a0 = A.molecule_radius;
+    const double vthermal = sqrt(8.0 * A.k_B * temperature / (M_PI * m0));
+    const double cross_section = M_PI * (a0 * a0);
+    const double nu = 1.0 / 3.0 * m0 * vthermal / cross_section;
+    const double l = m0 / M_PI / (a0 * a0) / rho;
+    const double c_s = vthermal * sqrt(M_PI / 8.0);
+    const double Kn = 0.5 * l / radius;
+    const double Ma = vrel / c_s;
+    const double Re = 2.0 * radius * rho * vrel / nu;
+    const double CdE = 2.0 * sqrt(Ma * Ma + 128.0 / 9.0 / M_PI);
+    // the Stokes coefficient's four branches: the power shared by the first three is one call with selected operands
+    const double pw = pow(Re <= 1.e-3 ? 2.0 * radius * rho / nu : Re, Re <= 500.0 ? -0.313 : 1.397);
+    double CdS;
+    if (Re <= 1.e-3)
+        CdS = 24.0 * nu / (2.0 * radius * rho * c_s) + 3.6 / c_s * pow(vrel, 0.687) * pw;
+    else if (Re <= 500.0)
+        CdS = 24.0 * Ma / Re + 3.6 * Ma * pw;
+    else if (Re <= 1500.0)
+        CdS = Ma * 9.5e-5 * pw;
+    else
+        CdS = Ma * 2.61;
+    const double Cd = (9.0 * Kn * Kn * CdE + CdS) / (3.0 * Kn + 1.0) / (3.0 * Kn + 1.0);
+    // the reference's die() guards (:1163-1208): the particle stays as it was and is reported
+    int guard = 0;
+    if (Ma < 1.e-20)
+        guard = 1;
+    else if (Ma > 1.e20)
+        guard = 2;
+    else if (CdE < 1.e-20)
+        guard = 3;
+    else if (CdE > 1.e20)
+        guard = 4;
+    else if (CdS < 1.e-30)
+        guard = 5;
+    else if (CdS > 1.e30)
+        guard = 6;
+    else if (Cd < 1.e-20)
+        guard = 7;
+    else if (Cd > 1.e20)
+        guard = 8;
+    if (guard) {
+        *A.status = (unsigned long long)guard | ((unsigned long long)n << 8); // any one of the tripped particles
+        return;
+    }
+    const double tstop = 4.0 * l * A.particle_density / (3.0 * rho * Cd * c_s * Kn);
+
+    // ---- calculate_dust_smoothing: H of cell (rmed_id(r1), inf_azimuthal_id(phi1)) ------------------------------
+    const int is = ib_raw < 0 ? 0 : ib_raw; // (<= nr-1 already)
+    const double H_dust = particle_scale_height<ADI>(P, is, ja) * sqrt(P.alpha / (P.alpha + stokes_old));
+    const double epsilon_sq = (H_dust * P.thickness_smoothing) * (H_dust * P.thickness_smoothing);
+
+    // ---- gravity of the bodies, star included -------------------------------------------------------------------
+    double grav_r_ddot = 0.0, minus_grav_l_dot = 0.0;
+    if (A.gravity_cartesian) {
+        double s, c;
+        sincos(phi1, &s, &c);
+        const double x = r1 * c, y = r1 * s;
+        double ax = 0.0, ay = 0.0;
+        for (int k = 0; k < P.nbodies; ++k) {
+            const double x_dist = x - P.bx[k], y_dist = y - P.by[k];
+            const double dist2 = x_dist * x_dist + y_dist * y_dist + epsilon_sq;
+            const double dist = sqrt(dist2);
+            ax += -P.G * P.bm[k] * x_dist / (dist * dist2);
+            ay += -P.G * P.bm[k] * y_dist / (dist * dist2);
+        }
+        grav_r_ddot = ax * c + ay * s;
+        minus_grav_l_dot = (-ax * s + ay * c) * r1;
+    } else {
+        for (int k = 0; k < P.nbodies; ++k) {
+            double s, c;
+            sincos(phi1 - A.bphi[k], &s, &c);
+            const double rp = A.br[k];
+            const double d = sqrt(r1 * r1 + rp * rp - 2.0 * r1 * rp * c);
+            const double d2s = d * d + epsilon_sq;
+            grav_r_ddot -= P.G * P.bm[k] * (r1 - rp * c) / (d2s * d);
+            minus_grav_l_dot -= P.G * P.bm[k] * r1 * rp * s / (d2s * d);
+        }
+    }
+
+    // ---- kick: exponential propagator (Mignone et al. 2019, eq. 33) ---------------------------------------------
+    const double exp_tstop = exp(-dt / tstop);
+    const double h1 = tstop * (-expm1(-dt / tstop));
+    double l2 = exp_tstop * l0 + h1 * minus_grav_l_dot;
+    l2 += h1 * (minus_l_rel + l0) / tstop;
+    double r_dot2 = exp_tstop * r_dot0;
+    r_dot2 += h1 * 0.5 * (l0 * l0 + l2 * l2) / (r1 * r1 * r1);
+    r_dot2 += h1 * grav_r_ddot;
+    r_dot2 += h1 * (minus_r_dotel_r + r_dot0) / tstop;
+    // second half drift
+    const double r3 = r1 + r_dot2 * hfdt;
+    double phi3 = particle_check_angle(phi1 + 0.5 * (l2 / (r1 * r1) + l2 / (r3 * r3)) * hfdt);
+    // move(): escaped particles leave; rotate(): the frame's turn over the step
+    const double r3sq = r3 * r3;
+    if (r3sq > A.escape_max_sq || r3sq < A.escape_min_sq)
+        A.alive[n] = 0;
+    phi3 = particle_check_angle(phi3 - A.frame_angle);
+    A.r[n] = r3;
+    A.phi[n] = phi3;
+    A.r_dot[n] = r_dot2;
+    A.phi_dot[n] = l2 / r3sq;
+    A.stokes[n] = tstop * sqrt(P.G * P.Mc / (r3 * r3 * r3));
+}

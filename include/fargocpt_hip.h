@@ -452,6 +452,64 @@ int fcpt_init_physics(fcpt_ctx *ctx);
  * t = 0 grids into FCPT_F_*0, then this call). */
 int fcpt_recalculate_derived(fcpt_ctx *ctx);
 
+/* ---- Lagrangian dust particles with gas drag ---------------------------------------------------------------
+ * particles::integrate with ParticleIntegrator: midpoint (integrate_exponential_midpoint, src/particles/
+ * particles.cpp:1579-1672, after Zhu et al. 2014 and Mignone et al. 2019) on one radial slab, for the host-stepped
+ * loop: per step fcpt_set_bodies, fcpt_particles_step, fcpt_step, fcpt_post -- the particle step reads the gas at the
+ * start of the hydro step, where the reference calls it (src/simulation.cpp:177-180).  fcpt_run_steps does not
+ * advance particles.  A context that never receives particles launches nothing for them.
+ *
+ * Departure from the reference: a particle beyond Rmed[Nr-1] makes the reference read row Nr of a scalar grid (out
+ * of bounds); here the lower row of the cell-centred interpolation is clamped to [0, Nr-2] (linear extrapolation
+ * from the last two rows, the mirror of the release build's behaviour below Rmed[0]) and that of v_r to [0, Nr-1].
+ * Not covered (the host driver refuses setups that ask for them): the explicit adaptive integrator, dust diffusion, disk
+ * gravity on particles, Cartesian particle state, leapfrog, several slabs. */
+typedef struct fcpt_particle_params {
+    double particle_density;  /* ParticleDensity (code units) */
+    double molecule_mass;     /* mu * m_u (code units), calc_tstop's m0 (particles.cpp:1139) */
+    double molecule_radius;   /* 1.5e-8 cm in code units (particles.cpp:1147) */
+    double k_B;               /* Boltzmann's constant (code units) */
+    double escape_radius_min; /* ParticleMinimumEscapeRadius, inside [rmin, rmax] of the descriptor */
+    double escape_radius_max; /* ParticleMaximumEscapeRadius */
+    int32_t gravity_cartesian; /* 1: the bodies' pull in Cartesian form (particles.cpp:1020-1060: CartesianParticles: yes
+                                * with the midpoint integrator, parameters.cpp:927-932), 0: polar form (:981-1018) */
+    int32_t _pad0;
+} fcpt_particle_params;
+
+/* The values of the default unit system (L0 = 1 au, M0 = 1 solMass; fcpt_desc_default) for d->mu, escape radii at
+ * d->rmin / d->rmax, polar gravity.  No GPU needed. */
+int fcpt_particle_params_default(const fcpt_desc *d, fcpt_particle_params *out);
+
+/* Replace the particles of the context by n particles (host arrays of n entries each, copied; the caller's order is
+ * kept: slot k holds particle k).  r, phi: position; r_dot, phi_dot: dr/dt and dphi/dt; radius: grain radius;
+ * stokes: the Stokes number of the previous step (enters the smoothing length, particles.cpp:896-912; check_tstop's
+ * value at the start).  n = 0 removes them.  FCPT_EINVAL: a context that is one of several slabs, escape radii
+ * outside [rmin, rmax] or not ordered, a null array.  Blocks. */
+int fcpt_particles_set(fcpt_ctx *ctx, const fcpt_particle_params *params, int64_t n, const uint64_t *id, const double *r,
+                       const double *phi, const double *r_dot, const double *phi_dot, const double *radius,
+                       const double *stokes);
+
+/* One launch on the context's stream, no host wait: update_velocities_from_indirect_term (particles.cpp:1326-1341)
+ * with (indirect_x, indirect_y), integrate_exponential_midpoint over dt with the gas grids as they are and the bodies
+ * of the last fcpt_set_bodies (star included), the escape test of move() (:2019-2031: a particle with r^2 beyond the
+ * squared escape radii -/+ DBL_EPSILON is dead from then on) and rotate (:2394-2395) by frame_angle (= OmegaFrame dt).
+ * Where the reference's calc_tstop would die() (Ma, CdE, CdS, Cd outside their ranges, :1163-1208) nothing of the
+ * particle is written in that step -- neither the indirect term's kick nor the rotation by frame_angle, so in a rotating
+ * frame it stays behind its neighbours -- and its id and the guard (1 .. 8 in the order of the source) are kept for the
+ * next blocking call.  If several particles trip a guard between two blocking calls, any one of them is the one
+ * reported (plain stores of the lanes to one status word: which one is not deterministic).
+ * In the column search an angle whose product with Nphi / 2 pi rounds up to Nphi stays in the last column (the reference
+ * wraps it to column 0 and extrapolates v_phi over a whole turn there). */
+int fcpt_particles_step(fcpt_ctx *ctx, double dt, double indirect_x, double indirect_y, double frame_angle);
+
+/* Block until the queued particle steps are done.  _count: the number of live particles.  _get: the live particles in
+ * ascending slot order (arrays of `capacity` entries, any of them may be NULL; FCPT_EINVAL if capacity is too small,
+ * *n then tells the need).  Both return FCPT_EINVAL once when a guard was tripped since the last blocking call
+ * (fcpt_last_error names the particle's id and the guard), and work again afterwards. */
+int fcpt_particles_count(fcpt_ctx *ctx, int64_t *n_alive);
+int fcpt_particles_get(fcpt_ctx *ctx, int64_t capacity, uint64_t *id, double *r, double *phi, double *r_dot, double *phi_dot,
+                       double *radius, double *stokes, int64_t *n);
+
 /* ---- the hot path -------------------------------------------------------- */
 
 /* cfl::condition_cfl without the MPI_Allreduce (src/cfl.cpp:185-376): the
