@@ -371,6 +371,22 @@ class Context:
             self._call("source_chunks", out.ctypes.data_as(C.POINTER(_i32)), _i32(n.value), C.byref(n))
         return out
 
+    def last_nshift(self) -> np.ndarray:
+        """Integer FARGO shift of every ring in the last transport (libraries that export last_nshift: the oracle)."""
+        if not self.lib.has("last_nshift"):
+            raise AttributeError("this library does not export last_nshift")
+        out = np.zeros(self.nr, dtype=np.int32)
+        self._call("last_nshift", out.ctypes.data_as(C.POINTER(_i32)))
+        return out
+
+    def last_ntilde(self) -> np.ndarray:
+        """The same shifts before rounding (libraries that export last_ntilde: the oracle)."""
+        if not self.lib.has("last_ntilde"):
+            raise AttributeError("this library does not export last_ntilde")
+        out = np.zeros(self.nr)
+        self._call("last_ntilde", _as_dp(out))
+        return out
+
     # radial slabs over RCCL inside the library
     def comm_init(self, unique_id: bytes):
         assert len(unique_id) == COMM_ID_BYTES

@@ -62,6 +62,7 @@ struct orc_ctx {
     double *rmp, *rmm, *lp, *lm, *vres, *vmean, *work, *qrstar /* vector */, *densstar /* vector */,
         *tempshift, *dq;
     int *nshift;
+    double *ntilde; /* the unrounded shifts of the last transport */
     int *nosplit;
     /* cfl scratch (cfl.cpp:11-12) */
     double *cfl_vmean, *cfl_vres;
@@ -687,6 +688,7 @@ int orc_create(const fcpt_desc *d, const double *radii, orc_ctx **out)
     c->tempshift = dalloc(ns);
     c->dq = dalloc(ns);
     c->nshift = (int *)calloc((size_t)c->nr, sizeof(int));
+    c->ntilde = dalloc((size_t)c->nr);
     c->nosplit = (int *)calloc((size_t)c->nr, sizeof(int));
     c->cfl_vmean = dalloc((size_t)c->nr + 1);
     c->cfl_vres = dalloc(ns);
@@ -714,7 +716,7 @@ int orc_destroy(orc_ctx *c)
                      &c->trp,        &c->qplus,     &c->qminus,      &c->density_int, &c->tau_eff, &c->nusig, &c->nusig_rp, &c->cfac_phi, &c->cfac_r,
                      &c->rmp,        &c->rmm,       &c->lp,          &c->lm,          &c->vres,
                      &c->vmean,      &c->work,      &c->qrstar,      &c->densstar,    &c->tempshift,
-                     &c->dq,         &c->cfl_vmean, &c->cfl_vres,    &c->massflow,
+                     &c->dq,         &c->cfl_vmean, &c->cfl_vres,    &c->massflow,  &c->ntilde,
                      &c->accel_r,    &c->accel_az};
     for (size_t i = 0; i < sizeof(ps) / sizeof(ps[0]); ++i)
         free(*ps[i]);
@@ -809,6 +811,14 @@ int orc_last_nshift(const orc_ctx *c, int32_t *out)
         return FCPT_EINVAL;
     for (int i = 0; i < c->nr; ++i)
         out[i] = c->nshift[i];
+    return FCPT_OK;
+}
+int orc_last_ntilde(const orc_ctx *c, double *out)
+{
+    if (!c || !out)
+        return FCPT_EINVAL;
+    for (int i = 0; i < c->nr; ++i)
+        out[i] = c->ntilde[i];
     return FCPT_OK;
 }
 int orc_set_bodies(orc_ctx *c, int32_t n, const double *x, const double *y, const double *m,
@@ -2278,6 +2288,7 @@ static void OneWindTheta(orc_ctx *c, double dt)
         const double Ntilde = c->vmean[i] * c->InvRmed[i] * dt * c->invdphi;
         const double Nround = floor(Ntilde + 0.5);
         c->nshift[i] = (int)Nround;
+        c->ntilde[i] = Ntilde;
         for (int j = 0; j < Nphi; j++)
             c->vazi[IDX(c, i, j)] = (Ntilde - Nround) * c->Rmed[i] * invdt * c->dphi;
         if (!c->d.fast_transport) {

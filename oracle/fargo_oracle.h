@@ -58,6 +58,8 @@ int orc_run_steps(orc_ctx *c, int64_t nsteps, int32_t snap, int64_t *nsteps_done
 int orc_geometry(const orc_ctx *c, int32_t which, double *out);
 /* per-ring integer shifts of the last transport call (TransportEuler.cpp:207-236) */
 int orc_last_nshift(const orc_ctx *c, int32_t *out);
+/* the same shifts before rounding, Ntilde = <v_phi> dt / (Rmed dphi): Nshift = floor(Ntilde + 0.5) */
+int orc_last_ntilde(const orc_ctx *c, double *out);
 
 #ifdef __cplusplus
 }
