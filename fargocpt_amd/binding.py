@@ -109,6 +109,11 @@ class ParticleParams(C.Structure):
                 ("escape_radius_min", _f64), ("escape_radius_max", _f64), ("gravity_cartesian", _i32), ("_pad0", _i32)]
 
 
+class ParticleDiffusion(C.Structure):
+    """fcpt_particle_diffusion: the switches of drag and diffusion, the Philox key and the counter of the next step."""
+    _fields_ = [("gas_drag", _i32), ("diffusion", _i32), ("seed", _u64), ("step", _u64)]
+
+
 PARTICLE_FIELDS = ("r", "phi", "r_dot", "phi_dot", "radius", "stokes")
 
 
@@ -180,6 +185,23 @@ class Library:
         p = ParticleParams()
         self.check(self.fn("particle_params_default")(C.byref(d), C.byref(p)), "particle_params_default")
         return p
+
+    def philox4x32(self, counter, key) -> np.ndarray:
+        """Ten rounds of Philox4x32 on the host: counter (4 words), key (2 words) -> 4 words."""
+        c = (C.c_uint32 * 4)(*[int(v) for v in counter])
+        k = (C.c_uint32 * 2)(*[int(v) for v in key])
+        out = (C.c_uint32 * 4)()
+        f = self.fn("philox4x32")
+        f.restype = None
+        f(c, k, out)
+        return np.array(out[:], dtype=np.uint32)
+
+    def particles_std_normal(self, seed: int, pid: int, step: int) -> float:
+        """The deviate of the diffusion kick for (seed, particle id, step), on the host."""
+        f = self.fn("particles_std_normal")
+        f.restype = _f64
+        f.argtypes = [_u64, _u64, _u64]
+        return f(int(seed), int(pid), int(step))
 
     def kernel_names(self):
         n = self.fn("kernel_count")()
@@ -486,6 +508,23 @@ class Context:
         out = {"id": ids[:n.value].copy()}
         out.update({k: v[:n.value].copy() for k, v in a.items()})
         return out
+
+    def particles_diffusion(self, gas_drag: bool = True, diffusion: bool = False, seed: int = 0, step: int = 0):
+        """ParticleGasDragEnabled / ParticleDustDiffusion, the Philox key and the counter of the next particles_step."""
+        p = ParticleDiffusion(int(bool(gas_drag)), int(bool(diffusion)), int(seed), int(step))
+        self._call("particles_diffusion", C.byref(p))
+
+    def particles_diffusion_get(self) -> ParticleDiffusion:
+        p = ParticleDiffusion()
+        self._call("particles_diffusion_get", C.byref(p))
+        return p
+
+    def particles_normals(self, step: int) -> np.ndarray:
+        """The deviates the live particles draw at counter `step` (particles_get's order); nothing is stepped."""
+        cap = self.particles_count()
+        snv = np.zeros(cap)
+        self._call("particles_normals", _u64(int(step)), C.c_int64(cap), _as_dp(snv))
+        return snv
 
     def allreduce_sum(self, values) -> np.ndarray:
         """SUM over the slabs of the communicator (the same bits on every slab); without one: the input."""

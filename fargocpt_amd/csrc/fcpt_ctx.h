@@ -104,6 +104,7 @@ struct fcpt_ctx {
     // dust particles (fcpt_particles.hip): device arrays and parameters of k_particles_step (part.n = 0: none), the ids
     // by slot, the one device block behind all of them
     ParticleArgs part = {};
+    fcpt_particle_diffusion part_diff = {1, 0, 0, 0}; // outlives fcpt_particles_set; step counts fcpt_particles_step calls
     unsigned long long *part_id = nullptr;
     void *part_block = nullptr;
     // fcpt_run_steps on launch-bound grids: a captured hipGraph of `graph_cycle` consecutive steps (the out-of-place

@@ -4,6 +4,7 @@
 // Reference counterparts are cited per function (paths relative to the
 // reference's src/).
 #include "fcpt_internal.h"
+#include "kernels/philox.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -413,6 +414,17 @@ int fcpt_particle_params_default(const fcpt_desc *d, fcpt_particle_params *out)
     out->escape_radius_max = d->rmax;
     out->gravity_cartesian = 0;
     return FCPT_OK;
+}
+
+// the dust-diffusion kick's generator as the kernel compiles it (kernels/philox.h)
+void fcpt_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])
+{
+    fcpt::philox4x32_10(ctr, key, out);
+}
+
+double fcpt_particles_std_normal(uint64_t seed, uint64_t id, uint64_t step)
+{
+    return fcpt::particle_std_normal(seed, id, step);
 }
 
 int fcpt_split_domain(const fcpt_desc *d, fcpt_split *out)

@@ -290,6 +290,10 @@ struct ParticleArgs {
     // the bodies of the last fcpt_set_bodies in polar coordinates (t_planet::get_r / get_phi)
     double br[FCPT_MAX_BODIES], bphi[FCPT_MAX_BODIES];
     double dt, indirect_x, indirect_y, frame_angle;
+    // fcpt_particles_diffusion: which form of k_particles_step runs, and what its kick draws from (kernels/philox.h)
+    int gas_drag, diffusion;
+    const unsigned long long *id;
+    unsigned long long seed, step;
 };
 
 } // namespace fcpt

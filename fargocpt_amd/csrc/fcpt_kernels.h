@@ -88,6 +88,8 @@ struct DiskBodies {
 size_t disk_on_bodies_blocks(const Dev &P); // blocks of the first stage: `part` holds 4 * n * blocks doubles, `out` 4 * n
 void launch_disk_on_bodies(const Dev &P, int n, const DiskBodies &B, double *part, double *out, hipStream_t st);
 void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st);
+void launch_particles_normals(int n, const unsigned long long *id, unsigned long long seed, unsigned long long step, double *snv,
+                              hipStream_t st);
 void launch_source_fused(const Dev &P, hipStream_t st);
 int launch_source_march(const Dev &P, hipStream_t st, bool fold_bc, bool *bc_folded, bool fold_cfl = false);
 void launch_cfl_final(const Dev &P, int apply_policy, hipStream_t st);

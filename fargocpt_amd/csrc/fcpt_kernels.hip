@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "fcpt_kernels.h"
+#include "kernels/philox.h"
 
 namespace fcpt {
 

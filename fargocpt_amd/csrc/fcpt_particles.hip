@@ -1,8 +1,9 @@
-// Dust particles of the C ABI: device state, the launch of k_particles_step (kernels/particles.h) and the blocking
-// reads.  Replaces particles::integrate with ParticleIntegrator: midpoint (particles/particles.cpp:1525-1557,1579-1672)
+// Dust particles of the C ABI: device state, the launch of k_particles_step (kernels/particles.h), the switches of
+// drag and diffusion and the blocking reads.  Replaces particles::integrate with ParticleIntegrator: midpoint (particles/particles.cpp:1525-1557,1579-1672)
 // for one radial slab; see include/fargocpt_hip.h for what is and is not covered.
 #include "fcpt_ctx.h"
 
+#include <algorithm>
 #include <cfloat>
 
 namespace fcpt {
@@ -43,6 +44,14 @@ int particles_wait(fcpt_ctx *c, const char *who)
     return FCPT_EINVAL;
 }
 
+// the Philox counter holds the id: two particles with one id would receive the same kicks
+bool ids_distinct(const unsigned long long *id, size_t n)
+{
+    std::vector<unsigned long long> v(id, id + n);
+    std::sort(v.begin(), v.end());
+    return std::adjacent_find(v.begin(), v.end()) == v.end();
+}
+
 } // namespace
 
 extern "C" {
@@ -68,6 +77,10 @@ int fcpt_particles_set(fcpt_ctx *c, const fcpt_particle_params *prm, int64_t n, 
                   !(prm->escape_radius_min < prm->escape_radius_max))) {
         set_error("fcpt_particles_set: escape radii [%g, %g] must be ordered and inside the grid [%g, %g]", prm->escape_radius_min,
                   prm->escape_radius_max, c->d.rmin, c->d.rmax);
+        return FCPT_EINVAL;
+    }
+    if (n > 0 && c->part_diff.diffusion && !ids_distinct((const unsigned long long *)id, (size_t)n)) {
+        set_error("fcpt_particles_set: particle ids must be distinct while dust diffusion is on (the id is the random counter)");
         return FCPT_EINVAL;
     }
     HIPCHK(hipStreamSynchronize(c->stream)); // a queued step may still use the arrays
@@ -134,6 +147,7 @@ int fcpt_particles_step(fcpt_ctx *c, double dt, double indirect_x, double indire
 {
     if (!c)
         return FCPT_EINVAL;
+    const unsigned long long step = c->part_diff.step++;
     if (c->part.n <= 0)
         return FCPT_OK;
     join_side(c);
@@ -148,6 +162,11 @@ int fcpt_particles_step(fcpt_ctx *c, double dt, double indirect_x, double indire
     A.indirect_x = indirect_x;
     A.indirect_y = indirect_y;
     A.frame_angle = frame_angle;
+    A.gas_drag = c->part_diff.gas_drag;
+    A.diffusion = c->part_diff.diffusion;
+    A.id = c->part_id;
+    A.seed = c->part_diff.seed;
+    A.step = step;
     launch_particles(P, A, c->stream);
     HIPCHK(hipGetLastError());
     return FCPT_OK;
@@ -209,6 +228,75 @@ int fcpt_particles_get(fcpt_ctx *c, int64_t capacity, uint64_t *id, double *r, d
                 out[q][k] = host[q * nn + s];
         ++k;
     }
+    return FCPT_OK;
+}
+
+int fcpt_particles_diffusion(fcpt_ctx *c, const fcpt_particle_diffusion *p)
+{
+    if (!c || !p) {
+        set_error("fcpt_particles_diffusion: null argument");
+        return FCPT_EINVAL;
+    }
+    if ((p->gas_drag != 0 && p->gas_drag != 1) || (p->diffusion != 0 && p->diffusion != 1)) {
+        set_error("fcpt_particles_diffusion: gas_drag = %d and diffusion = %d must be 0 or 1", p->gas_drag, p->diffusion);
+        return FCPT_EINVAL;
+    }
+    if (p->diffusion && c->part.n > 0) {
+        std::vector<unsigned long long> ids((size_t)c->part.n);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(ids.data(), c->part_id, ids.size() * 8, hipMemcpyDeviceToHost));
+        if (!ids_distinct(ids.data(), ids.size())) {
+            set_error("fcpt_particles_diffusion: particle ids must be distinct while dust diffusion is on (the id is the random counter)");
+            return FCPT_EINVAL;
+        }
+    }
+    c->part_diff = *p;
+    return FCPT_OK;
+}
+
+int fcpt_particles_diffusion_get(fcpt_ctx *c, fcpt_particle_diffusion *out)
+{
+    if (!c || !out)
+        return FCPT_EINVAL;
+    *out = c->part_diff;
+    return FCPT_OK;
+}
+
+int fcpt_particles_normals(fcpt_ctx *c, uint64_t step, int64_t capacity, double *snv)
+{
+    if (!c || capacity < 0 || (capacity > 0 && !snv))
+        return FCPT_EINVAL;
+    if (c->part.n <= 0)
+        return FCPT_OK;
+    const size_t nn = (size_t)c->part.n;
+    double *d_snv = nullptr;
+    if (hipMalloc((void **)&d_snv, nn * sizeof(double)) != hipSuccess) {
+        set_error("hipMalloc(%zu bytes) for the deviates failed", nn * sizeof(double));
+        return FCPT_ENOMEM;
+    }
+    launch_particles_normals(c->part.n, c->part_id, c->part_diff.seed, step, d_snv, c->stream);
+    std::vector<double> host(nn);
+    std::vector<unsigned char> alive(nn);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(host.data(), d_snv, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(alive.data(), c->part.alive, nn, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_snv);
+    HIPCHK(e);
+    int64_t m = 0;
+    for (unsigned char a : alive)
+        m += a != 0;
+    if (m > capacity) {
+        set_error("fcpt_particles_normals: %lld live particles, room for %lld", (long long)m, (long long)capacity);
+        return FCPT_EINVAL;
+    }
+    size_t k = 0;
+    for (size_t s = 0; s < nn; ++s)
+        if (alive[s])
+            snv[k++] = host[s];
     return FCPT_OK;
 }
 

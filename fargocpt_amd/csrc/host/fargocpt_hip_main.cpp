@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -465,6 +466,7 @@ void config_to_desc(const Config &c, fcpt_desc &d)
 // Dust particles: the Particle* keys of parameters.cpp:853-961 with their units and defaults
 struct ParticleSetup {
     bool on = false, cartesian_gravity = false;
+    bool gas_drag = true, diffusion = false; // ParticleGasDragEnabled, ParticleDustDiffusion (with --dust-seed)
     long n = 0;
     int species = 1;
     double radius = 0, radius_factor = 10, eccentricity = 0, density = 0, slope = 0;
@@ -696,10 +698,19 @@ int main(int argc, char **argv)
     bool quiet = false, lenient = false;
     long max_steps = -1, restart_from = -1;
     int want_ranks = 1;
+    bool have_dust_seed = false, bad_dust_seed = false;
+    unsigned long long dust_seed = 0;
     std::string mode, cfgpath, transport = "auto", bodies_mode = "circular";
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
-        if (a == "-q")
+        if (a == "--dust-seed") { // unsigned 64-bit, decimal: the key of the diffusion kicks' generator
+            const std::string v = i + 1 < argc ? argv[++i] : "";
+            char *end = nullptr;
+            errno = 0;
+            dust_seed = strtoull(v.c_str(), &end, 10);
+            bad_dust_seed = v.empty() || v.find_first_not_of("0123456789") != std::string::npos || errno == ERANGE || *end;
+            have_dust_seed = true;
+        } else if (a == "-q")
             quiet = true;
         else if (a == "--lenient")
             lenient = true;
@@ -721,9 +732,11 @@ int main(int argc, char **argv)
     // start_mode.cpp:29-113: start | restart [N] | auto
     if ((mode != "start" && mode != "restart" && mode != "auto") || cfgpath.empty() || want_ranks < 1 ||
         (transport != "auto" && transport != "rccl" && transport != "host") ||
-        (bodies_mode != "circular" && bodies_mode != "free")) {
+        (bodies_mode != "circular" && bodies_mode != "free") || bad_dust_seed) {
+        if (bad_dust_seed)
+            fprintf(stderr, "fargocpt_hip: --dust-seed needs an unsigned 64-bit integer\n");
         fprintf(stderr, "usage: fargocpt_hip [-q] [--lenient] [-N steps] [--ranks n] [--transport auto|rccl|host] "
-                        "[--bodies circular|free] start|auto|restart [N] <config.yml>\n");
+                        "[--bodies circular|free] [--dust-seed N] start|auto|restart [N] <config.yml>\n");
         return 2;
     }
     // this process's rank: FCPT_RANK / FCPT_NRANKS from the --ranks parent below or from a launcher of the caller's
@@ -787,10 +800,22 @@ int main(int argc, char **argv)
         };
         if (std::tolower(cfg.str("ParticleIntegrator", "m")[0]) != 'm')
             return refuse("ParticleIntegrator other than midpoint (the explicit adaptive integrator)");
-        if (!cfg.flag("ParticleGasDragEnabled", true))
-            return refuse("ParticleGasDragEnabled: no");
-        if (cfg.flag("ParticleDustDiffusion", false))
-            return refuse("ParticleDustDiffusion");
+        // dust diffusion is a stochastic run: it needs --dust-seed, there is no hidden default.  The drag may be
+        // switched off only together with it (the reference's dust_diffusion test).
+        ps.diffusion = cfg.flag("ParticleDustDiffusion", false);
+        ps.gas_drag = cfg.flag("ParticleGasDragEnabled", true);
+        const char *seed_hint = "fargocpt_hip: (ParticleDustDiffusion: yes runs with --dust-seed N, the seed of its random kicks"
+                                "; ParticleGasDragEnabled: no only together with it)\n";
+        if (!ps.gas_drag && !(ps.diffusion && have_dust_seed)) {
+            const int rc = refuse("ParticleGasDragEnabled: no");
+            fputs(seed_hint, stderr);
+            return rc;
+        }
+        if (ps.diffusion && !have_dust_seed) {
+            const int rc = refuse("ParticleDustDiffusion");
+            fputs(seed_hint, stderr);
+            return rc;
+        }
         if (cfg.flag("ParticleDiskGravityEnabled", false))
             return refuse("ParticleDiskGravityEnabled");
         if (lower(cfg.str("ParticleSurfaceDensitySlope", "SigmaSlope")) == "gas")
@@ -997,7 +1022,9 @@ int main(int argc, char **argv)
     // which the reference takes as the velocity change of the hydro centre over the step divided by dt
     // (ComputeIndirectTermNbody, frame_of_reference.cpp:138-160) -- for circular orbits the time average of
     // G m r_p / a^3 over [t, t + dt], in closed form.
-    const bool indirect = lower(cfg.str("HydroFrameCenter", "primary")) == "primary";
+    // (HydroFrameCenter: all with a single body is the same centre)
+    const std::string frame_center = lower(cfg.str("HydroFrameCenter", "primary"));
+    const bool indirect = frame_center == "primary" || (frame_center == "all" && cfg.nbody.size() == 1);
     double step_itx = 0.0, step_ity = 0.0; // the indirect term of the step being set up: the particles feel it too
     auto set_bodies = [&](double t, double dt) {
         double x[FCPT_MAX_BODIES], y[FCPT_MAX_BODIES], m[FCPT_MAX_BODIES], rsm[FCPT_MAX_BODIES];
@@ -1622,6 +1649,13 @@ int main(int argc, char **argv)
         last_dt = clk0.last_dt;
     }
     CHECK(fcpt_dt_statistics(ctx, nullptr, nullptr, 1));
+    if (ps.on && (ps.diffusion || !ps.gas_drag)) {
+        // One particle step per hydro iteration: the generator's counter is the iteration count, set here -- after the
+        // zero-length step of the initial Stokes numbers, and from misc.bin on a restart -- so that a run continued from
+        // a snapshot with the same seed draws the same deviates.
+        const fcpt_particle_diffusion pd = {ps.gas_drag ? 1 : 0, ps.diffusion ? 1 : 0, (uint64_t)dust_seed, (uint64_t)n_iter};
+        CHECK(fcpt_particles_diffusion(ctx, &pd));
+    }
     while (time < t_final) {
         if (max_steps >= 0 && (long)n_iter >= max_steps)
             break;

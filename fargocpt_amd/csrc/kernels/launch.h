@@ -539,7 +539,20 @@ void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st)
     if (A.n <= 0)
         return;
     const dim3 grid((A.n + 255) / 256), block(256);
-    with_bool(P.adiabatic, [&](auto ADI) { KLAUNCH(KID_PARTICLES, k_particles_step<TARG(ADI)>, grid, block, P, A); });
+    with_bool(P.adiabatic, [&](auto ADI) {
+        with_bool(A.gas_drag != 0, [&](auto DRAG) {
+            with_bool(A.diffusion != 0, [&](auto DIFF) {
+                KLAUNCH(KID_PARTICLES, (k_particles_step<TARG(ADI), TARG(DRAG), TARG(DIFF)>), grid, block, P, A);
+            });
+        });
+    });
+}
+
+void launch_particles_normals(int n, const unsigned long long *id, unsigned long long seed, unsigned long long step, double *snv,
+                              hipStream_t st)
+{
+    if (n > 0)
+        hipLaunchKernelGGL(k_particles_normals, dim3((n + 255) / 256), dim3(256), 0, st, n, id, seed, step, snv);
 }
 
 // rings whose CFL terms read nothing the ghost exchange or the boundary kernels write: ring i reads rows i

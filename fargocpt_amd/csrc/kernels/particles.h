@@ -1,4 +1,5 @@
-// Part of fcpt_kernels.hip (one translation unit, namespace fcpt): Lagrangian dust particles with gas drag.
+// Part of fcpt_kernels.hip (one translation unit, namespace fcpt): Lagrangian dust particles with gas drag
+// and turbulent diffusion.
 // Not a stand-alone header: included once, in the order given there.
 //
 // k_particles_step restates, per particle and statement by statement (paths relative to the reference's src/):
@@ -9,6 +10,8 @@
 //     calculate_derivitives_from_star_and_planets(_in_cart) :981-1060
 //   the escape test of move()             particles/particles.cpp:2019-2031
 //   rotate                                particles/particles.cpp:2394-2395
+//   diffuse_dust, kick_length             particles/dust_diffusion.cpp:29-97, with the deviate of kernels/philox.h
+//   check_tstop                           particles/particles.cpp:1277-1311  (drag off, diffusion on)
 //
 // Shape: one lane per live particle, structure-of-arrays state, no atomics, no LDS, no waits between workgroups.
 // The ring and column of a particle differ from lane to lane, so the per-ring arrays are read through plain vector
@@ -99,30 +102,17 @@ __device__ __forceinline__ double particle_bilinear(double Qmm, double Qpm, doub
     return ((rp - r) * Qm + (r - rm) * Qp) / (rp - rm);
 }
 
-template <bool ADI> __global__ void __launch_bounds__(256) k_particles_step(const Dev P, const ParticleArgs A)
+// The gas at (r_tmp, phi1), r_tmp inside the grid: find_nearest + the four bilinear interpolations of
+// interpolate_quantities (:1216-1244).  ib_raw and ja are the cell of calculate_dust_smoothing.
+struct ParticleGasAt {
+    double rho, temperature, vg_radial, vg_azimuthal;
+    int ib_raw, ja;
+};
+template <bool ADI>
+__device__ __forceinline__ ParticleGasAt particle_interpolate(const Dev &P, const ParticleArgs &A, double r_tmp, double phi1)
 {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= A.n || !A.alive[n])
-        return;
-    const double dt = A.dt;
-    const double r0 = A.r[n], phi0 = A.phi[n], radius = A.radius[n], stokes_old = A.stokes[n];
-    double r_dot0, phi_dot0;
-    { // update_velocities_from_indirect_term
-        double s, c;
-        sincos(phi0, &s, &c);
-        r_dot0 = A.r_dot[n] + dt * (A.indirect_x * c + A.indirect_y * s);
-        phi_dot0 = A.phi_dot[n] + dt * (-A.indirect_x * s + A.indirect_y * c) / r0;
-    }
-    const double l0 = r0 * r0 * phi_dot0;
-    const double hfdt = 0.5 * dt;
-    // half drift
-    const double r1 = r0 + r_dot0 * hfdt;
-    const double phi1 = particle_check_angle(phi0 + 0.5 * (l0 / (r0 * r0) + l0 / (r1 * r1)) * hfdt);
-
-    // ---- gas at (r_tmp, phi1): find_nearest + four bilinear interpolations ------------------------------------
     const int nr = P.nr, nphi = P.nphi;
     const double *Rinf = P.Rinf.p, *Rmed = P.Rmed.p;
-    const double r_tmp = fmin(fmax(r1, Rinf[0]), Rinf[nr]); // Rsup[nr-1] = Rinf[nr]
     const int ia = particle_rinf_id(Rinf, nr, A, r_tmp);
     const int ib_raw = r_tmp >= Rmed[ia] ? ia : ia - 1; // Rinf[ia] < Rmed[ia] < Rinf[ia+1]
     const int ib = ib_raw < 0 ? 0 : (ib_raw > nr - 2 ? nr - 2 : ib_raw);
@@ -152,21 +142,23 @@ template <bool ADI> __global__ void __launch_bounds__(256) k_particles_step(cons
 
     const ParticleGas gmm = particle_gas<ADI>(P, ib, jb), gpm = particle_gas<ADI>(P, ib + 1, jb);
     const ParticleGas gmp = particle_gas<ADI>(P, ib, jbp), gpp = particle_gas<ADI>(P, ib + 1, jbp);
-    const double rho = particle_bilinear(gmm.rho, gpm.rho, gmp.rho, gpp.rho, rbm, rbp, phim_b, phip_b, P.dphi, r_tmp, phi1);
-    const double temperature = particle_bilinear(gmm.T, gpm.T, gmp.T, gpp.T, rbm, rbp, phim_b, phip_b, P.dphi, r_tmp, phi1);
-    const double vg_radial = particle_bilinear(P.vrad[IDX(ia, jb)], P.vrad[IDX(ia + 1, jb)], P.vrad[IDX(ia, jbp)], P.vrad[IDX(ia + 1, jbp)],
-                                               ram, rap, phim_b, phip_b, P.dphi, r_tmp, phi1);
-    const double vg_azimuthal = particle_bilinear(P.vazi[IDX(ib, ja)], P.vazi[IDX(ib + 1, ja)], P.vazi[IDX(ib, jap)], P.vazi[IDX(ib + 1, jap)],
-                                                  rbm, rbp, phim_a, phip_a, P.dphi, r_tmp, phi1) +
-                                r_tmp * P.omega_frame;
+    ParticleGasAt g;
+    g.rho = particle_bilinear(gmm.rho, gpm.rho, gmp.rho, gpp.rho, rbm, rbp, phim_b, phip_b, P.dphi, r_tmp, phi1);
+    g.temperature = particle_bilinear(gmm.T, gpm.T, gmp.T, gpp.T, rbm, rbp, phim_b, phip_b, P.dphi, r_tmp, phi1);
+    g.vg_radial = particle_bilinear(P.vrad[IDX(ia, jb)], P.vrad[IDX(ia + 1, jb)], P.vrad[IDX(ia, jbp)], P.vrad[IDX(ia + 1, jbp)], ram, rap,
+                                    phim_b, phip_b, P.dphi, r_tmp, phi1);
+    g.vg_azimuthal = particle_bilinear(P.vazi[IDX(ib, ja)], P.vazi[IDX(ib + 1, ja)], P.vazi[IDX(ib, jap)], P.vazi[IDX(ib + 1, jap)], rbm,
+                                       rbp, phim_a, phip_a, P.dphi, r_tmp, phi1) +
+                     r_tmp * P.omega_frame;
+    g.ib_raw = ib_raw;
+    g.ja = ja;
+    return g;
+}
 
-    // calculate_gas_drag_expmid
-    const double minus_r_dotel_r = vg_radial - r_dot0;
-    const double minus_l_rel = r1 * vg_azimuthal - l0;
-    const double vrel_phi = vg_azimuthal - phi_dot0 * r0;
-    const double vrel = sqrt(minus_r_dotel_r * minus_r_dotel_r + vrel_phi * vrel_phi);
-
-    // ---- calc_tstop --------------------------------------------------------------------------------------------
+// calc_tstop (:1130-1214) -> the number of the reference's die() guard that trips (:1163-1208), or 0 and tstop
+__device__ __forceinline__ int particle_calc_tstop(const ParticleArgs &A, double radius, double rho, double vrel, double temperature,
+                                                   double &tstop)
+{
     const double m0 = A.molecule_mass, a0 = A.molecule_radius;
     const double vthermal = sqrt(8.0 * A.k_B * temperature / (M_PI * m0));
     const double cross_section = M_PI * (a0 * a0);
@@ -189,7 +181,6 @@ template <bool ADI> __global__ void __launch_bounds__(256) k_particles_step(cons
     else
         CdS = Ma * 2.61;
     const double Cd = (9.0 * Kn * Kn * CdE + CdS) / (3.0 * Kn + 1.0) / (3.0 * Kn + 1.0);
-    // the reference's die() guards (:1163-1208): the particle stays as it was and is reported
     int guard = 0;
     if (Ma < 1.e-20)
         guard = 1;
@@ -207,11 +198,80 @@ template <bool ADI> __global__ void __launch_bounds__(256) k_particles_step(cons
         guard = 7;
     else if (Cd > 1.e20)
         guard = 8;
-    if (guard) {
-        *A.status = (unsigned long long)guard | ((unsigned long long)n << 8); // any one of the tripped particles
-        return;
+    if (guard)
+        return guard;
+    tstop = 4.0 * l * A.particle_density / (3.0 * rho * Cd * c_s * Kn);
+    return 0;
+}
+
+// Cell (i, j) for the diffusion kick: rho as particle_gas forms it, and D_g = alpha c_s H
+// (dust_diffusion.cpp:102-119; c_s is the sound speed of the EOS, H = c_s / (sqrt(gamma) Omega_K) for the ideal one)
+template <bool ADI> __device__ __forceinline__ double particle_rho(const Dev &P, int i, int j)
+{
+    return particle_gas<ADI>(P, i, j).rho;
+}
+template <bool ADI> __device__ __forceinline__ double particle_gas_diffusion(const Dev &P, int i, int j)
+{
+    if (ADI) {
+        const double cs = sqrt(P.gamma * (P.gamma - 1.0) * P.energy[IDX(i, j)] / P.sigma[IDX(i, j)]);
+        return P.alpha * cs * (cs / sqrt(P.gamma) * P.g_inv_omk.p[i]);
     }
-    const double tstop = 4.0 * l * A.particle_density / (3.0 * rho * Cd * c_s * Kn);
+    const double cs = P.cs_ring.p[i];
+    return P.alpha * cs * (cs * P.g_inv_omk.p[i]);
+}
+
+// DRAG: ParticleGasDragEnabled; DIFF: ParticleDustDiffusion (the Brownian radial kick of dust_diffusion.cpp:29-97 after
+// Charnoz et al. 2011, between the midpoint step and move()).  <ADI, true, false> is the drag-only step.
+// With the drag off tstop = 1e100 and exp_tstop and h1 are formed from it as the reference writes them; the Stokes
+// number of the step is then 1e100 Omega_K(r3) (DIFF off, :1671) or check_tstop's (:1277-1311, DIFF on, :1549-1551):
+// a second interpolation, at the end position, and calc_tstop with the velocities of the end of the step.
+// DEPARTURE from the reference: rho, d rho / dr and D_g of the kick come from the current Sigma (and e); the reference
+// evaluates them at init and refreshes them only under Disk: yes, from a RHO it refreshes only with the drag on.
+template <bool ADI, bool DRAG, bool DIFF> __global__ void __launch_bounds__(256) k_particles_step(const Dev P, const ParticleArgs A)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= A.n || !A.alive[n])
+        return;
+    const double dt = A.dt;
+    const double r0 = A.r[n], phi0 = A.phi[n], radius = A.radius[n], stokes_old = A.stokes[n];
+    double r_dot0, phi_dot0;
+    { // update_velocities_from_indirect_term
+        double s, c;
+        sincos(phi0, &s, &c);
+        r_dot0 = A.r_dot[n] + dt * (A.indirect_x * c + A.indirect_y * s);
+        phi_dot0 = A.phi_dot[n] + dt * (-A.indirect_x * s + A.indirect_y * c) / r0;
+    }
+    const double l0 = r0 * r0 * phi_dot0;
+    const double hfdt = 0.5 * dt;
+    // half drift
+    const double r1 = r0 + r_dot0 * hfdt;
+    const double phi1 = particle_check_angle(phi0 + 0.5 * (l0 / (r0 * r0) + l0 / (r1 * r1)) * hfdt);
+
+    const int nr = P.nr, nphi = P.nphi;
+    const double *Rinf = P.Rinf.p, *Rmed = P.Rmed.p;
+    const double r_tmp = fmin(fmax(r1, Rinf[0]), Rinf[nr]); // Rsup[nr-1] = Rinf[nr]
+    double tstop = 1e100, minus_r_dotel_r = 0.0, minus_l_rel = 0.0;
+    int ib_raw, ja;
+    if (DRAG) {
+        const ParticleGasAt g = particle_interpolate<ADI>(P, A, r_tmp, phi1);
+        ib_raw = g.ib_raw;
+        ja = g.ja;
+        // calculate_gas_drag_expmid
+        minus_r_dotel_r = g.vg_radial - r_dot0;
+        minus_l_rel = r1 * g.vg_azimuthal - l0;
+        const double vrel_phi = g.vg_azimuthal - phi_dot0 * r0;
+        const double vrel = sqrt(minus_r_dotel_r * minus_r_dotel_r + vrel_phi * vrel_phi);
+        // the reference's die() guards: the particle stays as it was and is reported
+        if (const int guard = particle_calc_tstop(A, radius, g.rho, vrel, g.temperature, tstop)) {
+            *A.status = (unsigned long long)guard | ((unsigned long long)n << 8); // any one of the tripped particles
+            return;
+        }
+    } else { // the cell of the smoothing length alone
+        const int ia = particle_rinf_id(Rinf, nr, A, r_tmp);
+        ib_raw = r_tmp >= Rmed[ia] ? ia : ia - 1;
+        ja = (int)floor(phi1 * P.invdphi);
+        ja = ja < 0 ? 0 : (ja > nphi - 1 ? nphi - 1 : ja);
+    }
 
     // ---- calculate_dust_smoothing: H of cell (rmed_id(r1), inf_azimuthal_id(phi1)) ------------------------------
     const int is = ib_raw < 0 ? 0 : ib_raw; // (<= nr-1 already)
@@ -250,22 +310,76 @@ template <bool ADI> __global__ void __launch_bounds__(256) k_particles_step(cons
     const double exp_tstop = exp(-dt / tstop);
     const double h1 = tstop * (-expm1(-dt / tstop));
     double l2 = exp_tstop * l0 + h1 * minus_grav_l_dot;
-    l2 += h1 * (minus_l_rel + l0) / tstop;
+    if (DRAG)
+        l2 += h1 * (minus_l_rel + l0) / tstop;
     double r_dot2 = exp_tstop * r_dot0;
     r_dot2 += h1 * 0.5 * (l0 * l0 + l2 * l2) / (r1 * r1 * r1);
     r_dot2 += h1 * grav_r_ddot;
-    r_dot2 += h1 * (minus_r_dotel_r + r_dot0) / tstop;
+    if (DRAG)
+        r_dot2 += h1 * (minus_r_dotel_r + r_dot0) / tstop;
     // second half drift
     const double r3 = r1 + r_dot2 * hfdt;
     double phi3 = particle_check_angle(phi1 + 0.5 * (l2 / (r1 * r1) + l2 / (r3 * r3)) * hfdt);
-    // move(): escaped particles leave; rotate(): the frame's turn over the step
-    const double r3sq = r3 * r3;
-    if (r3sq > A.escape_max_sq || r3sq < A.escape_min_sq)
+    if (!DIFF) {
+        // move(): escaped particles leave; rotate(): the frame's turn over the step
+        const double r3sq = r3 * r3;
+        if (r3sq > A.escape_max_sq || r3sq < A.escape_min_sq)
+            A.alive[n] = 0;
+        phi3 = particle_check_angle(phi3 - A.frame_angle);
+        A.r[n] = r3;
+        A.phi[n] = phi3;
+        A.r_dot[n] = r_dot2;
+        A.phi_dot[n] = l2 / r3sq;
+        A.stokes[n] = tstop * sqrt(P.G * P.Mc / (r3 * r3 * r3));
+        return;
+    }
+    const double phi_dot3 = l2 / (r3 * r3);
+    const double omega_k3 = sqrt(P.G * P.Mc / (r3 * r3 * r3));
+    if (!DRAG) { // check_tstop at the end position
+        const ParticleGasAt g = particle_interpolate<ADI>(P, A, fmin(fmax(r3, Rinf[0]), Rinf[nr]), phi3);
+        const double dv_r = g.vg_radial - r_dot2;
+        const double dv_phi = g.vg_azimuthal - phi_dot3 * r3;
+        if (const int guard = particle_calc_tstop(A, radius, g.rho, sqrt(dv_r * dv_r + dv_phi * dv_phi), g.temperature, tstop)) {
+            *A.status = (unsigned long long)guard | ((unsigned long long)n << 8);
+            return;
+        }
+    }
+    const double stokes = tstop * omega_k3;
+    // ---- diffuse_dust / kick_length: values of the particle's cell, no interpolation -------------------------------
+    const double St2 = stokes * stokes;
+    const double Sc = (1.0 + St2) * (1.0 + St2) / (1.0 + 4.0 * St2); // Youdin & Lithwick 2007, eq. 37
+    const int ik = particle_rinf_id(Rinf, nr, A, r3);
+    int jk = (int)floor(phi3 * P.invdphi);
+    jk = jk < 0 ? 0 : (jk > nphi - 1 ? nphi - 1 : jk);
+    const double Dd = particle_gas_diffusion<ADI>(P, ik, jk) / Sc;
+    const double rho = particle_rho<ADI>(P, ik, jk);
+    // compute_gas_density_radial_derivative: rows 0 and Nr-1 stay zero
+    double drho_dr = 0.0;
+    if (ik >= 1 && ik <= nr - 2)
+        drho_dr = (particle_rho<ADI>(P, ik + 1, jk) - particle_rho<ADI>(P, ik - 1, jk)) / (Rmed[ik + 1] - Rmed[ik - 1]);
+    const double mean = Dd / rho * drho_dr * dt * dt * omega_k3;
+    const double sigma = sqrt(2.0 * Dd * dt);
+    const double snv = particle_std_normal(A.seed, A.id[n], A.step);
+    const double q = sigma * snv / r3;
+    const double corr_2d = r3 * (sqrt(1.0 + q * q) - 1.0); // the missing diffusion tangential to r
+    const double r4 = r3 + (mean + snv * sigma + corr_2d);
+    // move() on the kicked radius (r4 <= 0 has left as well); rotate()
+    const double r4sq = r4 * r4;
+    if (r4sq > A.escape_max_sq || r4sq < A.escape_min_sq || !(r4 > 0.0))
         A.alive[n] = 0;
     phi3 = particle_check_angle(phi3 - A.frame_angle);
-    A.r[n] = r3;
+    A.r[n] = r4;
     A.phi[n] = phi3;
     A.r_dot[n] = r_dot2;
-    A.phi_dot[n] = l2 / r3sq;
-    A.stokes[n] = tstop * sqrt(P.G * P.Mc / (r3 * r3 * r3));
+    A.phi_dot[n] = phi_dot3 * pow(r3 / r4, 1.5); // a circular orbit stays one
+    A.stokes[n] = stokes;
+}
+
+// the deviates of fcpt_particles_normals: what k_particles_step<., ., true> draws at counter `step`, per slot
+__global__ void __launch_bounds__(256) k_particles_normals(int n, const unsigned long long *id, unsigned long long seed,
+                                                           unsigned long long step, double *snv)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < n)
+        snv[k] = particle_std_normal(seed, id[k], step);
 }

@@ -452,7 +452,7 @@ int fcpt_init_physics(fcpt_ctx *ctx);
  * t = 0 grids into FCPT_F_*0, then this call). */
 int fcpt_recalculate_derived(fcpt_ctx *ctx);
 
-/* ---- Lagrangian dust particles with gas drag ---------------------------------------------------------------
+/* ---- Lagrangian dust particles with gas drag and diffusion ---------------------------------------------------------------
  * particles::integrate with ParticleIntegrator: midpoint (integrate_exponential_midpoint, src/particles/
  * particles.cpp:1579-1672, after Zhu et al. 2014 and Mignone et al. 2019) on one radial slab, for the host-stepped
  * loop: per step fcpt_set_bodies, fcpt_particles_step, fcpt_step, fcpt_post -- the particle step reads the gas at the
@@ -462,7 +462,7 @@ int fcpt_recalculate_derived(fcpt_ctx *ctx);
  * Departure from the reference: a particle beyond Rmed[Nr-1] makes the reference read row Nr of a scalar grid (out
  * of bounds); here the lower row of the cell-centred interpolation is clamped to [0, Nr-2] (linear extrapolation
  * from the last two rows, the mirror of the release build's behaviour below Rmed[0]) and that of v_r to [0, Nr-1].
- * Not covered (the host driver refuses setups that ask for them): the explicit adaptive integrator, dust diffusion, disk
+ * Not covered (the host driver refuses setups that ask for them): the explicit adaptive integrator, disk
  * gravity on particles, Cartesian particle state, leapfrog, several slabs. */
 typedef struct fcpt_particle_params {
     double particle_density;  /* ParticleDensity (code units) */
@@ -509,6 +509,44 @@ int fcpt_particles_step(fcpt_ctx *ctx, double dt, double indirect_x, double indi
 int fcpt_particles_count(fcpt_ctx *ctx, int64_t *n_alive);
 int fcpt_particles_get(fcpt_ctx *ctx, int64_t capacity, uint64_t *id, double *r, double *phi, double *r_dot, double *phi_dot,
                        double *radius, double *stokes, int64_t *n);
+
+/* Turbulent diffusion of the dust as a random walk (ParticleDustDiffusion: yes; src/particles/dust_diffusion.cpp:29-97,
+ * Charnoz et al. 2011 eq. 17) and ParticleGasDragEnabled.  With diffusion on, fcpt_particles_step ends, before the
+ * escape test, with the radial kick
+ *   dr = D_d / rho  d rho / dr  dt^2 Omega_K + snv sigma + r (sqrt(1 + (sigma snv / r)^2) - 1),  sigma = sqrt(2 D_d dt),
+ *   D_d = alpha c_s H / Sc,  Sc = (1 + St^2)^2 / (1 + 4 St^2),  phi_dot *= (r_old / r_new)^1.5
+ * from the values of the particle's cell (row of get_rinf_id, no interpolation; d rho / dr is the central difference
+ * over Rmed and zero in rows 0 and Nr-1; alpha is ViscousAlpha whatever the viscosity law).  A kicked radius <= 0
+ * counts as escaped.
+ * snv is a standard normal deviate that depends only on (seed, particle id, step): Philox4x32-10 with
+ *   counter = (id low, id high, step low, step high), key = (seed low, seed high),
+ *   u1 = ((w0 << 20 | w1 >> 12) + 0.5) 2^-52, u2 likewise from (w2, w3), snv = sqrt(-2 log u1) cos(2 pi u2),
+ * so the result does not depend on the slot order or on where a run was restarted.  `step` is advanced by one by every
+ * fcpt_particles_step, whatever the switches and also when there are no particles.  Ids must be distinct while
+ * diffusion is on: fcpt_particles_diffusion and fcpt_particles_set return FCPT_EINVAL otherwise.
+ * With gas_drag = 0 the stopping time is 1e100 and no drag term is applied (particles.cpp:1616-1656); the Stokes number
+ * the step leaves is 1e100 Omega_K(r) without diffusion and, with it, that of check_tstop (:1277-1311) at the end
+ * position, whose guards are reported as those of the drag step.
+ * Departure from the reference: rho, d rho / dr and D_g are formed from the current Sigma (and e); the reference
+ * evaluates them at init and refreshes them only under Disk: yes (from a RHO that follows the gas only with the drag
+ * on).  The two agree for frozen gas.
+ * The settings belong to the context and outlive fcpt_particles_set.  A context that never calls
+ * fcpt_particles_diffusion steps with {1, 0, 0, 0}. */
+typedef struct fcpt_particle_diffusion {
+    int32_t gas_drag;  /* 1 (default) | 0: ParticleGasDragEnabled */
+    int32_t diffusion; /* 0 (default) | 1: ParticleDustDiffusion */
+    uint64_t seed;     /* Philox key */
+    uint64_t step;     /* Philox counter of the next fcpt_particles_step */
+} fcpt_particle_diffusion;
+int fcpt_particles_diffusion(fcpt_ctx *ctx, const fcpt_particle_diffusion *p);
+int fcpt_particles_diffusion_get(fcpt_ctx *ctx, fcpt_particle_diffusion *out); /* with the current step */
+/* The deviates the live particles would draw at counter `step` with the context's seed, in fcpt_particles_get's order
+ * (one small launch; nothing is stepped).  capacity as for fcpt_particles_get. */
+int fcpt_particles_normals(fcpt_ctx *ctx, uint64_t step, int64_t capacity, double *snv);
+
+/* The generator itself, on the host (no GPU needed): ten rounds of Philox4x32, and the deviate above. */
+void fcpt_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+double fcpt_particles_std_normal(uint64_t seed, uint64_t id, uint64_t step);
 
 /* ---- the hot path -------------------------------------------------------- */
 
