@@ -114,7 +114,14 @@ class ParticleDiffusion(C.Structure):
     _fields_ = [("gas_drag", _i32), ("diffusion", _i32), ("seed", _u64), ("step", _u64)]
 
 
+class ParticleIntegrator(C.Structure):
+    """fcpt_particle_integrator: midpoint (0) or explicit adaptive (1), its Cartesian state and its attempt cap."""
+    _fields_ = [("kind", _i32), ("cartesian", _i32), ("max_attempts", _i32), ("_pad0", _i32)]
+
+
+INTEGRATOR_MIDPOINT, INTEGRATOR_EXPLICIT = 0, 1
 PARTICLE_FIELDS = ("r", "phi", "r_dot", "phi_dot", "radius", "stokes")
+ADAPTIVE_FIELDS = ("timestep", "facold", "r_ddot", "phi_ddot")
 
 
 class FcptError(RuntimeError):
@@ -518,6 +525,41 @@ class Context:
         p = ParticleDiffusion()
         self._call("particles_diffusion_get", C.byref(p))
         return p
+
+    def particles_integrator(self, kind: int = INTEGRATOR_MIDPOINT, cartesian: bool = False, max_attempts: int = 0):
+        """ParticleIntegrator: midpoint (0) | explicit (1); cartesian: the state holds x, y, v_x, v_y; max_attempts: the cap
+        on accepted + rejected substeps per particle and call (0: 10000)."""
+        p = ParticleIntegrator(int(kind), int(bool(cartesian)), int(max_attempts), 0)
+        self._call("particles_integrator", C.byref(p))
+
+    def particles_integrator_get(self) -> ParticleIntegrator:
+        p = ParticleIntegrator()
+        self._call("particles_integrator_get", C.byref(p))
+        return p
+
+    def particles_timestep_init(self):
+        """Queues init_particle_timestep: the starting step size of every live particle, facold = 1e-4."""
+        self._call("particles_timestep_init")
+
+    def particles_adaptive_set(self, timestep, facold):
+        """Step size and facold of every slot of the last particles_set, in slot order (restart)."""
+        t = np.ascontiguousarray(timestep, dtype=np.float64)
+        f = np.ascontiguousarray(facold, dtype=np.float64)
+        assert t.shape == f.shape and t.ndim == 1
+        self._call("particles_adaptive_set", C.c_int64(t.size), _as_dp(t), _as_dp(f))
+
+    def particles_adaptive_get(self) -> dict:
+        """The explicit integrator's state of the live particles in slot order: {"timestep", "facold", "r_ddot", "phi_ddot":
+        float64[n], "accepted", "rejected": uint32[n] (substeps of the last call)}."""
+        cap = self.particles_count()
+        a = {k: np.zeros(cap) for k in ADAPTIVE_FIELDS}
+        cnt = {k: np.zeros(cap, dtype=np.uint32) for k in ("accepted", "rejected")}
+        n = C.c_int64()
+        self._call("particles_adaptive_get", C.c_int64(cap), *(_as_dp(a[k]) for k in ADAPTIVE_FIELDS),
+                   *(cnt[k].ctypes.data_as(C.POINTER(_u32)) for k in ("accepted", "rejected")), C.byref(n))
+        out = {k: v[:n.value].copy() for k, v in a.items()}
+        out.update({k: v[:n.value].copy() for k, v in cnt.items()})
+        return out
 
     def particles_normals(self, step: int) -> np.ndarray:
         """The deviates the live particles draw at counter `step` (particles_get's order); nothing is stepped."""

@@ -107,6 +107,13 @@ struct fcpt_ctx {
     fcpt_particle_diffusion part_diff = {1, 0, 0, 0}; // outlives fcpt_particles_set; step counts fcpt_particles_step calls
     unsigned long long *part_id = nullptr;
     void *part_block = nullptr;
+    // ParticleIntegrator (outlives fcpt_particles_set) and the explicit integrator's arrays: a block of their own, made
+    // by fcpt_particles_timestep_init / _adaptive_set; part_adapt_set: the step size of every slot has been set since the
+    // last fcpt_particles_set
+    fcpt_particle_integrator part_integ = {0, 0, 0, 0};
+    ParticleAdaptive part_adapt = {};
+    void *part_adapt_block = nullptr;
+    bool part_adapt_set = false;
     // fcpt_run_steps on launch-bound grids: a captured hipGraph of `graph_cycle` consecutive steps (the out-of-place
     // transport swaps grid pointers, so the launch arguments repeat with period 2), replayed while the host-side state
     // that decided the launches (the whole Dev view, the lazy-evaluation flags) is what it was at capture

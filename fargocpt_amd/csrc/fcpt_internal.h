@@ -296,6 +296,15 @@ struct ParticleArgs {
     unsigned long long seed, step;
 };
 
+// the per-particle state of the explicit adaptive integrator (k_particles_step_explicit): a second device block,
+// made when first needed
+struct ParticleAdaptive {
+    double *timestep, *facold, *r_ddot, *phi_ddot;
+    unsigned int *accepted, *rejected; // substeps of the last call
+    int max_attempts;                  // guard 9: accepted + rejected substeps per particle and call
+    double rmin, rmax;                 // RMIN, RMAX of the descriptor: the drag kick is skipped outside (Rinf[0] < RMIN: ghost ring)
+};
+
 } // namespace fcpt
 
 #endif

@@ -23,7 +23,7 @@ enum KernelId {
     KID_TRANSPORT_FUSED, KID_MASSFLOW, KID_CFL_RINGS, KID_THETA_GATED_BOUNDARY, KID_EXCHANGE_COPY,
     KID_DISK_ON_BODY, KID_VISC_FACTORS, KID_SOURCE_MARCH_ADI, KID_SOURCE_MARCH_ADI_WIDE,
     KID_ACCEL_ON_GAS, KID_SOURCE_MARCH_ADI_ACC, KID_TRANSPORT_RADIAL_MEANS, KID_CFL_RINGS_BC,
-    KID_DISK_ON_BODIES, KID_PARTICLES, KID_COUNT
+    KID_DISK_ON_BODIES, KID_PARTICLES, KID_PARTICLES_EXPLICIT, KID_COUNT
 };
 static_assert(KID_COUNT <= 64, "fcpt_profile_start selects kernels with a 64-bit mask");
 extern const char *const kKernelNames[KID_COUNT];
@@ -88,6 +88,8 @@ struct DiskBodies {
 size_t disk_on_bodies_blocks(const Dev &P); // blocks of the first stage: `part` holds 4 * n * blocks doubles, `out` 4 * n
 void launch_disk_on_bodies(const Dev &P, int n, const DiskBodies &B, double *part, double *out, hipStream_t st);
 void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st);
+void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const ParticleAdaptive &X, bool cartesian, hipStream_t st);
+void launch_particles_timestep_init(const Dev &P, const ParticleArgs &A, const ParticleAdaptive &X, bool cartesian, hipStream_t st);
 void launch_particles_normals(int n, const unsigned long long *id, unsigned long long seed, unsigned long long step, double *snv,
                               hipStream_t st);
 void launch_source_fused(const Dev &P, hipStream_t st);

@@ -1,5 +1,6 @@
 // Dust particles of the C ABI: device state, the launch of k_particles_step (kernels/particles.h), the switches of
 // drag and diffusion and the blocking reads.  Replaces particles::integrate with ParticleIntegrator: midpoint (particles/particles.cpp:1525-1557,1579-1672)
+// and ParticleIntegrator: explicit (:1677-2014, k_particles_step_explicit)
 // for one radial slab; see include/fargocpt_hip.h for what is and is not covered.
 #include "fcpt_ctx.h"
 
@@ -15,14 +16,29 @@ void particles_free(fcpt_ctx *c)
     c->part_block = nullptr;
     c->part_id = nullptr;
     c->part = ParticleArgs{};
+    if (c->part_adapt_block)
+        (void)hipFree(c->part_adapt_block);
+    c->part_adapt_block = nullptr;
+    c->part_adapt = ParticleAdaptive{};
+    c->part_adapt_set = false;
 }
 
 } // namespace fcpt
 
 namespace {
 
-const char *const kGuardNames[9] = {"", "Ma < 1e-20", "Ma > 1e20", "CdE < 1e-20", "CdE > 1e20", "CdS < 1e-30",
-                                    "CdS > 1e30", "Cd < 1e-20",  "Cd > 1e20"};
+const char *const kGuardNames[11] = {"",
+                                     "Ma < 1e-20",
+                                     "Ma > 1e20",
+                                     "CdE < 1e-20",
+                                     "CdE > 1e20",
+                                     "CdS < 1e-30",
+                                     "CdS > 1e30",
+                                     "Cd < 1e-20",
+                                     "Cd > 1e20",
+                                     "the explicit integrator reached max_attempts substeps",
+                                     "t_stop < 10 dt: the drag is too stiff for the explicit kick"};
+const int kDefaultMaxAttempts = 10000;
 
 // waits for the queued steps; reports (once) a guard tripped since the last call
 int particles_wait(fcpt_ctx *c, const char *who)
@@ -39,9 +55,50 @@ int particles_wait(fcpt_ctx *c, const char *who)
     unsigned long long id = 0;
     if (slot < (size_t)c->part.n)
         HIPCHK(hipMemcpy(&id, c->part_id + slot, sizeof(id), hipMemcpyDeviceToHost));
-    set_error("%s: particle id %llu tripped guard %d of calc_tstop (%s) and was left unchanged", who, id, guard,
-              guard >= 1 && guard <= 8 ? kGuardNames[guard] : "?");
+    if (guard >= 9 && guard <= 10)
+        set_error("%s: particle id %llu tripped guard %d (%s) and was left unchanged", who, id, guard, kGuardNames[guard]);
+    else
+        set_error("%s: particle id %llu tripped guard %d of calc_tstop (%s) and was left unchanged", who, id, guard,
+                  guard >= 1 && guard <= 8 ? kGuardNames[guard] : "?");
     return FCPT_EINVAL;
+}
+
+// the explicit integrator's block, made when first needed: four double arrays and two counters per slot, zeroed
+int adaptive_alloc(fcpt_ctx *c)
+{
+    if (c->part_adapt_block)
+        return FCPT_OK;
+    const size_t nn = (size_t)c->part.n;
+    const size_t bytes = nn * 8 * 4 + nn * 4 * 2;
+    void *block = nullptr;
+    if (hipMalloc(&block, bytes) != hipSuccess) {
+        set_error("hipMalloc(%zu bytes) for the adaptive step sizes failed", bytes);
+        return FCPT_ENOMEM;
+    }
+    if (hipMemsetAsync(block, 0, bytes, c->stream) != hipSuccess) {
+        (void)hipFree(block);
+        set_error("hipMemsetAsync of the adaptive step sizes failed");
+        return FCPT_EHIP;
+    }
+    c->part_adapt_block = block;
+    double *arr = (double *)block;
+    ParticleAdaptive &X = c->part_adapt;
+    X.timestep = arr;
+    X.facold = arr + nn;
+    X.r_ddot = arr + 2 * nn;
+    X.phi_ddot = arr + 3 * nn;
+    X.accepted = (unsigned int *)(arr + 4 * nn);
+    X.rejected = X.accepted + nn;
+    return FCPT_OK;
+}
+
+// the bodies of the last fcpt_set_bodies in polar coordinates (t_planet::get_r / get_phi)
+void polar_bodies(const Dev &P, ParticleArgs &A)
+{
+    for (int k = 0; k < P.nbodies; ++k) {
+        A.br[k] = std::sqrt(P.bx[k] * P.bx[k] + P.by[k] * P.by[k]);
+        A.bphi[k] = std::atan2(P.by[k], P.bx[k]);
+    }
 }
 
 // the Philox counter holds the id: two particles with one id would receive the same kicks
@@ -150,14 +207,17 @@ int fcpt_particles_step(fcpt_ctx *c, double dt, double indirect_x, double indire
     const unsigned long long step = c->part_diff.step++;
     if (c->part.n <= 0)
         return FCPT_OK;
+    const bool explicit_adaptive = c->part_integ.kind == 1;
+    if (explicit_adaptive && !c->part_adapt_set) {
+        set_error("fcpt_particles_step: the explicit integrator has no step sizes since the last fcpt_particles_set: call "
+                  "fcpt_particles_timestep_init or fcpt_particles_adaptive_set first");
+        return FCPT_EINVAL;
+    }
     join_side(c);
     ProfScope prof_scope(c);
     ParticleArgs A = c->part;
     const Dev &P = c->P;
-    for (int k = 0; k < P.nbodies; ++k) { // t_planet::get_r / get_phi
-        A.br[k] = std::sqrt(P.bx[k] * P.bx[k] + P.by[k] * P.by[k]);
-        A.bphi[k] = std::atan2(P.by[k], P.bx[k]);
-    }
+    polar_bodies(P, A);
     A.dt = dt;
     A.indirect_x = indirect_x;
     A.indirect_y = indirect_y;
@@ -167,7 +227,15 @@ int fcpt_particles_step(fcpt_ctx *c, double dt, double indirect_x, double indire
     A.id = c->part_id;
     A.seed = c->part_diff.seed;
     A.step = step;
-    launch_particles(P, A, c->stream);
+    if (explicit_adaptive) {
+        ParticleAdaptive X = c->part_adapt;
+        X.max_attempts = c->part_integ.max_attempts > 0 ? c->part_integ.max_attempts : kDefaultMaxAttempts;
+        X.rmin = c->d.rmin;
+        X.rmax = c->d.rmax;
+        launch_particles_explicit(P, A, X, c->part_integ.cartesian != 0, c->stream);
+    } else {
+        launch_particles(P, A, c->stream);
+    }
     HIPCHK(hipGetLastError());
     return FCPT_OK;
 }
@@ -241,6 +309,11 @@ int fcpt_particles_diffusion(fcpt_ctx *c, const fcpt_particle_diffusion *p)
         set_error("fcpt_particles_diffusion: gas_drag = %d and diffusion = %d must be 0 or 1", p->gas_drag, p->diffusion);
         return FCPT_EINVAL;
     }
+    if (p->diffusion && c->part_integ.kind == 1) {
+        set_error("fcpt_particles_diffusion: dust diffusion is not available with the explicit adaptive integrator "
+                  "(fcpt_particles_integrator kind = 1)");
+        return FCPT_EINVAL;
+    }
     if (p->diffusion && c->part.n > 0) {
         std::vector<unsigned long long> ids((size_t)c->part.n);
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -259,6 +332,131 @@ int fcpt_particles_diffusion_get(fcpt_ctx *c, fcpt_particle_diffusion *out)
     if (!c || !out)
         return FCPT_EINVAL;
     *out = c->part_diff;
+    return FCPT_OK;
+}
+
+int fcpt_particles_integrator(fcpt_ctx *c, const fcpt_particle_integrator *p)
+{
+    if (!c || !p) {
+        set_error("fcpt_particles_integrator: null argument");
+        return FCPT_EINVAL;
+    }
+    if ((p->kind != 0 && p->kind != 1) || (p->cartesian != 0 && p->cartesian != 1)) {
+        set_error("fcpt_particles_integrator: kind = %d and cartesian = %d must be 0 or 1", p->kind, p->cartesian);
+        return FCPT_EINVAL;
+    }
+    if (p->max_attempts < 0) {
+        set_error("fcpt_particles_integrator: max_attempts = %d must not be negative (0 selects %d)", p->max_attempts,
+                  kDefaultMaxAttempts);
+        return FCPT_EINVAL;
+    }
+    if (p->cartesian && p->kind == 0) {
+        set_error("fcpt_particles_integrator: cartesian = 1 needs the explicit adaptive integrator (kind = 1); the midpoint "
+                  "integrator's Cartesian gravity is fcpt_particle_params.gravity_cartesian");
+        return FCPT_EINVAL;
+    }
+    if (p->kind == 1 && c->part_diff.diffusion) {
+        set_error("fcpt_particles_integrator: the explicit adaptive integrator is not available with dust diffusion "
+                  "(fcpt_particles_diffusion diffusion = 1)");
+        return FCPT_EINVAL;
+    }
+    c->part_integ = *p;
+    c->part_integ._pad0 = 0;
+    return FCPT_OK;
+}
+
+int fcpt_particles_integrator_get(fcpt_ctx *c, fcpt_particle_integrator *out)
+{
+    if (!c || !out)
+        return FCPT_EINVAL;
+    *out = c->part_integ;
+    return FCPT_OK;
+}
+
+int fcpt_particles_timestep_init(fcpt_ctx *c)
+{
+    if (!c)
+        return FCPT_EINVAL;
+    if (c->part_integ.kind != 1) {
+        set_error("fcpt_particles_timestep_init: select the explicit adaptive integrator first (fcpt_particles_integrator kind = 1)");
+        return FCPT_EINVAL;
+    }
+    if (c->part.n <= 0)
+        return FCPT_OK;
+    if (int rc = adaptive_alloc(c))
+        return rc;
+    join_side(c);
+    ParticleArgs A = c->part;
+    polar_bodies(c->P, A);
+    launch_particles_timestep_init(c->P, A, c->part_adapt, c->part_integ.cartesian != 0, c->stream);
+    HIPCHK(hipGetLastError());
+    c->part_adapt_set = true;
+    return FCPT_OK;
+}
+
+int fcpt_particles_adaptive_set(fcpt_ctx *c, int64_t n, const double *timestep, const double *facold)
+{
+    if (!c || !timestep || !facold) {
+        set_error("fcpt_particles_adaptive_set: null argument");
+        return FCPT_EINVAL;
+    }
+    if (n != (int64_t)c->part.n || n <= 0) {
+        set_error("fcpt_particles_adaptive_set: n = %lld, the context holds %d particle slots", (long long)n, c->part.n);
+        return FCPT_EINVAL;
+    }
+    if (int rc = adaptive_alloc(c))
+        return rc;
+    const size_t nn = (size_t)n;
+    HIPCHK(hipMemcpyAsync(c->part_adapt.timestep, timestep, nn * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->part_adapt.facold, facold, nn * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream)); // the caller's arrays are free again
+    c->part_adapt_set = true;
+    return FCPT_OK;
+}
+
+int fcpt_particles_adaptive_get(fcpt_ctx *c, int64_t capacity, double *timestep, double *facold, double *r_ddot, double *phi_ddot,
+                                uint32_t *accepted, uint32_t *rejected, int64_t *n)
+{
+    if (!c || !n || capacity < 0)
+        return FCPT_EINVAL;
+    *n = 0;
+    if (c->part.n <= 0)
+        return FCPT_OK;
+    if (!c->part_adapt_block) {
+        set_error("fcpt_particles_adaptive_get: no adaptive state since the last fcpt_particles_set");
+        return FCPT_EINVAL;
+    }
+    if (int rc = particles_wait(c, "fcpt_particles_adaptive_get"))
+        return rc;
+    const size_t nn = (size_t)c->part.n;
+    std::vector<unsigned char> alive(nn);
+    std::vector<double> host(4 * nn);
+    std::vector<unsigned int> counts(2 * nn);
+    HIPCHK(hipMemcpy(alive.data(), c->part.alive, nn, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(host.data(), c->part_adapt.timestep, 4 * nn * sizeof(double), hipMemcpyDeviceToHost)); // the first of four arrays
+    HIPCHK(hipMemcpy(counts.data(), c->part_adapt.accepted, 2 * nn * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    int64_t m = 0;
+    for (unsigned char a : alive)
+        m += a != 0;
+    *n = m;
+    if (m > capacity) {
+        set_error("fcpt_particles_adaptive_get: %lld live particles, room for %lld", (long long)m, (long long)capacity);
+        return FCPT_EINVAL;
+    }
+    double *out[4] = {timestep, facold, r_ddot, phi_ddot};
+    uint32_t *cnt[2] = {accepted, rejected};
+    size_t k = 0;
+    for (size_t s = 0; s < nn; ++s) {
+        if (!alive[s])
+            continue;
+        for (int q = 0; q < 4; ++q)
+            if (out[q])
+                out[q][k] = host[q * nn + s];
+        for (int q = 0; q < 2; ++q)
+            if (cnt[q])
+                cnt[q][k] = counts[q * nn + s];
+        ++k;
+    }
     return FCPT_OK;
 }
 

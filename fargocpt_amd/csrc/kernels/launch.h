@@ -13,7 +13,7 @@ const char *const kKernelNames[KID_COUNT] = {
     "k_transport_theta_march", "k_transport_fused", "k_massflow", "k_cfl_rings", "k_theta_march_gated_boundary",
     "k_exchange_copy", "k_disk_on_body", "k_visc_factors", "k_source_march_adi", "k_source_march_adi_wide",
     "k_accel_on_gas", "k_source_march_adi_acc",
-    "k_transport_radial_means", "k_cfl_rings_bc", "k_disk_on_bodies", "k_particles_step"};
+    "k_transport_radial_means", "k_cfl_rings_bc", "k_disk_on_bodies", "k_particles_step", "k_particles_step_explicit"};
 
 thread_local Profiler *g_prof = nullptr;
 
@@ -546,6 +546,28 @@ void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st)
             });
         });
     });
+}
+
+// ParticleIntegrator: explicit -- one lane per particle slot, one launch; the block size stands beside the kernel
+void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const ParticleAdaptive &X, bool cartesian, hipStream_t st)
+{
+    if (A.n <= 0)
+        return;
+    const dim3 grid((A.n + PARTICLES_EXPLICIT_BLOCK - 1) / PARTICLES_EXPLICIT_BLOCK), block(PARTICLES_EXPLICIT_BLOCK);
+    with_bool(P.adiabatic, [&](auto ADI) {
+        with_bool(A.gas_drag != 0, [&](auto DRAG) {
+            with_bool(cartesian, [&](auto CART) {
+                KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit<TARG(ADI), TARG(DRAG), TARG(CART)>), grid, block, P, A, X);
+            });
+        });
+    });
+}
+void launch_particles_timestep_init(const Dev &P, const ParticleArgs &A, const ParticleAdaptive &X, bool cartesian, hipStream_t st)
+{
+    if (A.n <= 0)
+        return;
+    const dim3 grid((A.n + PARTICLES_EXPLICIT_BLOCK - 1) / PARTICLES_EXPLICIT_BLOCK), block(PARTICLES_EXPLICIT_BLOCK);
+    with_bool(cartesian, [&](auto CART) { hipLaunchKernelGGL(k_particles_timestep_init<TARG(CART)>, grid, block, 0, st, P, A, X); });
 }
 
 void launch_particles_normals(int n, const unsigned long long *id, unsigned long long seed, unsigned long long step, double *snv,

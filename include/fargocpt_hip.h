@@ -462,8 +462,10 @@ int fcpt_recalculate_derived(fcpt_ctx *ctx);
  * Departure from the reference: a particle beyond Rmed[Nr-1] makes the reference read row Nr of a scalar grid (out
  * of bounds); here the lower row of the cell-centred interpolation is clamped to [0, Nr-2] (linear extrapolation
  * from the last two rows, the mirror of the release build's behaviour below Rmed[0]) and that of v_r to [0, Nr-1].
- * Not covered (the host driver refuses setups that ask for them): the explicit adaptive integrator, disk
- * gravity on particles, Cartesian particle state, leapfrog, several slabs. */
+ * ParticleIntegrator: explicit (integrate_explicit_adaptive, :1677-2014) with its CartesianParticles state is selected
+ * with fcpt_particles_integrator, below; the host driver does not offer it yet and still refuses the key.
+ * Not covered (the host driver refuses setups that ask for them): disk gravity on particles, leapfrog, several
+ * slabs. */
 typedef struct fcpt_particle_params {
     double particle_density;  /* ParticleDensity (code units) */
     double molecule_mass;     /* mu * m_u (code units), calc_tstop's m0 (particles.cpp:1139) */
@@ -543,6 +545,49 @@ int fcpt_particles_diffusion_get(fcpt_ctx *ctx, fcpt_particle_diffusion *out); /
 /* The deviates the live particles would draw at counter `step` with the context's seed, in fcpt_particles_get's order
  * (one small launch; nothing is stepped).  capacity as for fcpt_particles_get. */
 int fcpt_particles_normals(fcpt_ctx *ctx, uint64_t step, int64_t capacity, double *snv);
+
+/* ParticleIntegrator: explicit (integrate_explicit_adaptive, particles.cpp:1677-2014), the integrator for weakly coupled
+ * bodies (t_stop >= 10 dt).  With kind = 1 fcpt_particles_step queues, in one launch and per live particle:
+ * update_velocities_from_indirect_term (:1314-1343; the Cartesian form :1322-1324 with cartesian = 1); with gas_drag the
+ * explicit kick of update_velocities_from_gas_drag(_cart) (:1428-1504, :1345-1418: skipped for r < RMIN or r > RMAX, else
+ * v += dt a_drag and stokes = t_stop Omega_K(r), the gas interpolated as for the midpoint step with the same
+ * out-of-range departures); the embedded Cash-Karp RK5(4) over dt in substeps of the particle's own `timestep`
+ * (atol 1e-14, rtol 1e-12, Lund-stabilised controller, :1693-2012), the smoothing length recomputed every substep from
+ * the cell of the current position (:896-912) and the pull of the bodies of the last fcpt_set_bodies with the softening
+ * inside the square root (:914-952, or :954-979 with cartesian = 1); the escape test of move() on the squared distance
+ * (x^2 + y^2 with cartesian = 1); rotate (:2369-2397: position and velocity are turned with cartesian = 1).
+ * The controller is restated as written, with the aliasing of :1726: old_timestep refers to the stored step, which
+ * already holds the new value after :1981, so a rejection divides the stored step twice.
+ * cartesian = 1: r, phi, r_dot, phi_dot of fcpt_particles_set / _get hold x, y, v_x, v_y (CartesianParticles: yes).
+ * Guards, reported like those of calc_tstop and leaving the particle exactly as it was (timestep and facold included):
+ *   9   accepted + rejected substeps of one particle in one call reached max_attempts.  The reference's loop has no
+ *       bound; a NaN or zero step size would spin for ever.
+ *   10  t_stop < 10 dt in the drag kick.  Departure: check_tstop (:1303-1309) exits the reference on this condition once,
+ *       at start-up, and calls the explicit kick unstable below it; here it is held at every step.
+ * The step sizes live in a second device allocation made by fcpt_particles_timestep_init (queues
+ * init_particle_timestep, :248-374: Hairer's starting step with rsmooth = 0.05, facold = 1e-4) or
+ * fcpt_particles_adaptive_set (restart: n = the number of slots of the last fcpt_particles_set, slot order).
+ * fcpt_particles_set invalidates them: fcpt_particles_step with kind = 1 returns FCPT_EINVAL until one of the two has
+ * run.  fcpt_particles_adaptive_get blocks and hands out, for the live particles in slot order (any array may be NULL),
+ * the step size, facold, the accelerations of the last accepted substep and the accepted / rejected substeps of the last
+ * call.
+ * FCPT_EINVAL: kind = 1 while diffusion is on, and diffusion = 1 while kind = 1 (whichever call comes second; the
+ * refused call changes nothing); cartesian = 1 with kind = 0 (the midpoint integrator's Cartesian gravity remains
+ * fcpt_particle_params.gravity_cartesian); max_attempts < 0.
+ * The settings belong to the context and outlive fcpt_particles_set.  A context that never selects kind = 1 allocates
+ * and launches what it did before. */
+typedef struct fcpt_particle_integrator {
+    int32_t kind;         /* 0 midpoint (default) | 1 explicit adaptive */
+    int32_t cartesian;    /* explicit only: r, phi, r_dot, phi_dot hold x, y, vx, vy (CartesianParticles) */
+    int32_t max_attempts; /* explicit only; 0 = 10000 */
+    int32_t _pad0;
+} fcpt_particle_integrator;
+int fcpt_particles_integrator(fcpt_ctx *ctx, const fcpt_particle_integrator *p);
+int fcpt_particles_integrator_get(fcpt_ctx *ctx, fcpt_particle_integrator *out);
+int fcpt_particles_timestep_init(fcpt_ctx *ctx);
+int fcpt_particles_adaptive_set(fcpt_ctx *ctx, int64_t n, const double *timestep, const double *facold);
+int fcpt_particles_adaptive_get(fcpt_ctx *ctx, int64_t capacity, double *timestep, double *facold, double *r_ddot,
+                                double *phi_ddot, uint32_t *accepted, uint32_t *rejected, int64_t *n);
 
 /* The generator itself, on the host (no GPU needed): ten rounds of Philox4x32, and the deviate above. */
 void fcpt_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
