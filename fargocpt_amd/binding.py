@@ -561,6 +561,15 @@ class Context:
         out.update({k: v[:n.value].copy() for k, v in cnt.items()})
         return out
 
+    def particles_follow_run_steps(self, on: bool = True):
+        """run_steps also takes the particle step of every iteration (device-resident dt, frame angle and counter)."""
+        self._call("particles_follow_run_steps", _i32(int(bool(on))))
+
+    def particles_follow_run_steps_get(self) -> bool:
+        v = _i32()
+        self._call("particles_follow_run_steps_get", C.byref(v))
+        return bool(v.value)
+
     def particles_normals(self, step: int) -> np.ndarray:
         """The deviates the live particles draw at counter `step` (particles_get's order); nothing is stepped."""
         cap = self.particles_count()

@@ -29,6 +29,16 @@ using namespace fcpt; // private header of three translation units of namespace-
         }                                                                                   \
     } while (0)
 
+// The particle launch fcpt_run_steps queues in every iteration (fcpt_particles_follow_run_steps), without its per-step
+// scalars, which the kernel takes from the device clock: filled by particles_loop_launch(), launched by
+// enqueue_particles_loop(), and kept beside a captured graph to tell whether the graph still holds that launch.
+struct ParticleLaunch {
+    int on; // follow is switched on and there are particles; 0: everything below is zero
+    int explicit_adaptive, cartesian, adapt_set;
+    ParticleArgs A;
+    ParticleAdaptive X;
+};
+
 struct fcpt_ctx {
     fcpt_desc d;
     fcpt_split s;
@@ -114,6 +124,10 @@ struct fcpt_ctx {
     ParticleAdaptive part_adapt = {};
     void *part_adapt_block = nullptr;
     bool part_adapt_set = false;
+    // fcpt_particles_follow_run_steps (outlives fcpt_particles_set): fcpt_run_steps queues the particle step of every
+    // iteration; part_step_offset: the device word behind ParticleArgs::step_offset, made when first switched on
+    bool part_follow = false;
+    unsigned long long *part_step_offset = nullptr;
     // fcpt_run_steps on launch-bound grids: a captured hipGraph of `graph_cycle` consecutive steps (the out-of-place
     // transport swaps grid pointers, so the launch arguments repeat with period 2), replayed while the host-side state
     // that decided the launches (the whole Dev view, the lazy-evaluation flags) is what it was at capture
@@ -125,6 +139,7 @@ struct fcpt_ctx {
     bool graph_failed = false;
     Dev graph_P;
     unsigned graph_flags = 0;
+    ParticleLaunch graph_part = {}; // ... and the particle launch inside the cycle
 };
 
 
@@ -184,6 +199,9 @@ void enqueue_post(fcpt_ctx *c, bool may_defer_boundary = false);
 void flush_deferred_boundary(fcpt_ctx *c);
 // fcpt_particles.hip
 void particles_free(fcpt_ctx *c);
+int particles_loop_check(const fcpt_ctx *c);
+void particles_loop_launch(const fcpt_ctx *c, ParticleLaunch *L);
+void enqueue_particles_loop(fcpt_ctx *c);
 // fcpt_exchange.hip
 int enqueue_exchange(fcpt_ctx *c);
 int enqueue_cfl_allreduce(fcpt_ctx *c);

@@ -294,6 +294,10 @@ struct ParticleArgs {
     int gas_drag, diffusion;
     const unsigned long long *id;
     unsigned long long seed, step;
+    // fcpt_run_steps with fcpt_particles_follow_run_steps (null: the three per-step scalars are dt, frame_angle and step
+    // above): the step length is Dev::clk->dt, frame_angle the rounded product omega_frame * dt and the Philox counter
+    // *step_offset + clk->n_hydro_iter (wrapping), so a replayed hipGraph needs no new arguments
+    const unsigned long long *step_offset;
 };
 
 // the per-particle state of the explicit adaptive integrator (k_particles_step_explicit): a second device block,

@@ -92,6 +92,7 @@ void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const Partic
 void launch_particles_timestep_init(const Dev &P, const ParticleArgs &A, const ParticleAdaptive &X, bool cartesian, hipStream_t st);
 void launch_particles_normals(int n, const unsigned long long *id, unsigned long long seed, unsigned long long step, double *snv,
                               hipStream_t st);
+void launch_particles_counter_offset(unsigned long long *offset, unsigned long long counter, const DevClock *clk, hipStream_t st);
 void launch_source_fused(const Dev &P, hipStream_t st);
 int launch_source_march(const Dev &P, hipStream_t st, bool fold_bc, bool *bc_folded, bool fold_cfl = false);
 void launch_cfl_final(const Dev &P, int apply_policy, hipStream_t st);

@@ -111,7 +111,97 @@ bool ids_distinct(const unsigned long long *id, size_t n)
 
 } // namespace
 
+namespace fcpt {
+
+// what fcpt_run_steps refuses with follow on, before anything is queued
+int particles_loop_check(const fcpt_ctx *c)
+{
+    if (!c->part_follow)
+        return FCPT_OK;
+    if (c->d.integrator == FCPT_INTEGRATOR_LEAPFROG) {
+        set_error("fcpt_run_steps: fcpt_particles_follow_run_steps is on, and the particle step has no place in Integrator: "
+                  "Leapfrog (switch it off, or use Integrator: Euler)");
+        return FCPT_EINVAL;
+    }
+    if (c->part.n > 0 && c->part_integ.kind == 1 && !c->part_adapt_set) {
+        set_error("fcpt_run_steps: fcpt_particles_follow_run_steps is on, and the explicit integrator has no step sizes since "
+                  "the last fcpt_particles_set: call fcpt_particles_timestep_init or fcpt_particles_adaptive_set first");
+        return FCPT_EINVAL;
+    }
+    return FCPT_OK;
+}
+
+// The launch fcpt_particles_step would make from the context as it is, in its device-sourced form: dt, frame_angle and the
+// counter stay zero and step_offset is set (kernels/particles.h: particle_dt and its neighbours); the indirect term is the
+// one of the last fcpt_set_bodies.
+void particles_loop_launch(const fcpt_ctx *c, ParticleLaunch *L)
+{
+    std::memset((void *)L, 0, sizeof(*L));
+    if (!c->part_follow || c->part.n <= 0)
+        return;
+    L->on = 1;
+    L->explicit_adaptive = c->part_integ.kind == 1;
+    L->cartesian = c->part_integ.cartesian != 0;
+    L->adapt_set = c->part_adapt_set;
+    ParticleArgs &A = L->A;
+    std::memcpy((void *)&A, &c->part, sizeof(A));
+    polar_bodies(c->P, A);
+    A.dt = 0.0;
+    A.frame_angle = 0.0;
+    A.step = 0;
+    A.indirect_x = c->P.indirect_x;
+    A.indirect_y = c->P.indirect_y;
+    A.gas_drag = c->part_diff.gas_drag;
+    A.diffusion = c->part_diff.diffusion;
+    A.id = c->part_id;
+    A.seed = c->part_diff.seed;
+    A.step_offset = c->part_step_offset;
+    if (L->explicit_adaptive) {
+        std::memcpy((void *)&L->X, &c->part_adapt, sizeof(L->X));
+        L->X.max_attempts = c->part_integ.max_attempts > 0 ? c->part_integ.max_attempts : kDefaultMaxAttempts;
+        L->X.rmin = c->d.rmin;
+        L->X.rmax = c->d.rmax;
+    }
+}
+
+// the particle step of one iteration of fcpt_run_steps' device loop, behind the launch that left the step length in the clock
+void enqueue_particles_loop(fcpt_ctx *c)
+{
+    ParticleLaunch L;
+    particles_loop_launch(c, &L);
+    if (!L.on)
+        return;
+    join_side(c);
+    if (L.explicit_adaptive)
+        launch_particles_explicit(c->P, L.A, L.X, L.cartesian != 0, c->stream);
+    else
+        launch_particles(c->P, L.A, c->stream);
+}
+
+} // namespace fcpt
+
 extern "C" {
+
+int fcpt_particles_follow_run_steps(fcpt_ctx *c, int32_t on)
+{
+    if (!c || (on != 0 && on != 1)) {
+        set_error("fcpt_particles_follow_run_steps: null context, or on = %d is neither 0 nor 1", (int)on);
+        return FCPT_EINVAL;
+    }
+    if (on && !c->part_step_offset)
+        if (int rc = dev_alloc(c, &c->part_step_offset, 1))
+            return rc;
+    c->part_follow = on != 0;
+    return FCPT_OK;
+}
+
+int fcpt_particles_follow_run_steps_get(const fcpt_ctx *c, int32_t *on)
+{
+    if (!c || !on)
+        return FCPT_EINVAL;
+    *on = c->part_follow ? 1 : 0;
+    return FCPT_OK;
+}
 
 int fcpt_particles_set(fcpt_ctx *c, const fcpt_particle_params *prm, int64_t n, const uint64_t *id, const double *r,
                        const double *phi, const double *r_dot, const double *phi_dot, const double *radius,

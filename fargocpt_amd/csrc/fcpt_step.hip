@@ -492,10 +492,18 @@ void enqueue_device_step(fcpt_ctx *c)
     //  reduction -- but for k_potential, which reads no step length -- is that kernel; ring kernel of the reduction in use)
     const bool frog = c->d.integrator == FCPT_INTEGRATOR_LEAPFROG;
     const int want = c->P.opt.cfl_fold_in_source;
+    // (fcpt_particles_follow_run_steps with particles: their launch stands between the CFL reduction and the gas step
+    //  and reads the step length, which the fold would leave only in the source kernel's prologue: the policy launch)
+    const bool particles = c->part_follow && c->part.n > 0;
     const bool fold = (want < 0 ? (long long)c->P.nr * c->P.nphi < (1ll << 22) : want != 0) && !frog && c->fused_source &&
-                      c->march_source && source_march_applies(c->P) && cfl_by_rings(c->P);
+                      c->march_source && source_march_applies(c->P) && cfl_by_rings(c->P) && !particles;
     enqueue_cfl(c, fold ? 2 : 1);
     c->fold_pending = fold;
+    // the particle step where the reference has it (simulation.cpp:177-180): the step length is in force, the final
+    // boundary call of the step before has run (inside the CFL launch or ahead of it), the gas is that of the start of
+    // the step
+    if (particles)
+        enqueue_particles_loop(c);
     {
         // the gated launch of the fallback transport together with the final boundary call, where that call will be
         // nothing but the ghost-ring kernel and does not ride in the next CFL launch (grids below 4 M cells)
@@ -551,6 +559,7 @@ bool capture_graph(fcpt_ctx *c, int cycle)
     c->graph_cycle = cycle;
     c->graph_P = c->P;
     c->graph_flags = f0;
+    particles_loop_launch(c, &c->graph_part);
     return true;
 }
 } // namespace
@@ -563,7 +572,18 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
         return FCPT_EINVAL;
     ProfScope prof_scope(c);
     int64_t n = 0;
+    if (int rc = particles_loop_check(c)) { // fcpt_particles_follow_run_steps: refused before anything is queued
+        if (done)
+            *done = 0;
+        return rc;
+    }
     const bool slabs = c->comm && (c->peer_inner >= 0 || c->peer_outer >= 0); // this slab has neighbours
+    // fcpt_particles_follow_run_steps: the device loop counts the particle steps itself (the kernels add the clock's
+    // iteration count to an offset left here, once, outside any graph), and the host's counter follows when the steps are
+    // queued; the host-stepped branch calls fcpt_particles_step, which counts; without particles the counter still advances
+    const bool follow = c->part_follow, follow_dev = follow && !slabs && !snap && c->part.n > 0;
+    if (follow_dev && nsteps > 0)
+        launch_particles_counter_offset(c->part_step_offset, c->part_diff.step, c->P.clk, c->stream);
     if (slabs && !snap) {
         // several slabs, dt never leaves the device: CFL -> MIN over the slabs (cfl.cpp:379) -> policy kernel -> step
         // -> ghost exchange (simulation.cpp:236) -> post, all on one stream
@@ -619,8 +639,13 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
             // of the transport's ping-pong and the boundary call that rides in the next CFL launch (deferred inside
             // this function only) are put back by one or two plain steps -- the same two that let the lazily evaluated
             // grids settle before the first capture.
+            // The particle launch of the cycle (fcpt_particles_follow_run_steps) is compared as a whole too: the flag, the
+            // arrays and parameters of fcpt_particles_set, the drag, diffusion and integrator settings, the adaptive block.
+            ParticleLaunch part_now;
+            particles_loop_launch(c, &part_now);
             auto valid = [&] {
-                return c->graph_exec && std::memcmp(&c->graph_P, &c->P, sizeof(Dev)) == 0 && c->graph_flags == launch_flags(c);
+                return c->graph_exec && std::memcmp(&c->graph_P, &c->P, sizeof(Dev)) == 0 && c->graph_flags == launch_flags(c) &&
+                       std::memcmp(&c->graph_part, &part_now, sizeof(ParticleLaunch)) == 0;
             };
             for (int lead = 0; lead < 2 && !valid(); ++lead, ++n)
                 enqueue_device_step(c);
@@ -659,6 +684,9 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
             if (int rc = fcpt_snap_to_monitor(c, dt, &step_dt))
                 return rc;
             const double time_next_monitor = (k.n_monitor + 1) * c->d.monitor_timestep;
+            if (follow) // simulation.cpp:177-180, with the indirect term of the last fcpt_set_bodies
+                if (int rc = fcpt_particles_step(c, step_dt, c->P.indirect_x, c->P.indirect_y, c->d.omega_frame * step_dt))
+                    return rc;
             if (int rc = fcpt_step(c, step_dt))
                 return rc;
             if (int rc = fcpt_post(c, step_dt))
@@ -674,6 +702,8 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
             }
         }
     }
+    if (follow && (slabs || !snap))
+        c->part_diff.step += (unsigned long long)n;
     if (done)
         *done = n;
     return FCPT_OK;

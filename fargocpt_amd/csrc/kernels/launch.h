@@ -542,7 +542,9 @@ void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st)
     with_bool(P.adiabatic, [&](auto ADI) {
         with_bool(A.gas_drag != 0, [&](auto DRAG) {
             with_bool(A.diffusion != 0, [&](auto DIFF) {
-                KLAUNCH(KID_PARTICLES, (k_particles_step<TARG(ADI), TARG(DRAG), TARG(DIFF)>), grid, block, P, A);
+                with_bool(A.step_offset != nullptr, [&](auto DEV) { // (fcpt_run_steps: per-step scalars from the device clock)
+                    KLAUNCH(KID_PARTICLES, (k_particles_step<TARG(ADI), TARG(DRAG), TARG(DIFF), TARG(DEV)>), grid, block, P, A);
+                });
             });
         });
     });
@@ -557,7 +559,11 @@ void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const Partic
     with_bool(P.adiabatic, [&](auto ADI) {
         with_bool(A.gas_drag != 0, [&](auto DRAG) {
             with_bool(cartesian, [&](auto CART) {
-                KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit<TARG(ADI), TARG(DRAG), TARG(CART)>), grid, block, P, A, X);
+                if (A.step_offset)
+                    KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit_clock<TARG(ADI), TARG(DRAG), TARG(CART)>), grid, block, P,
+                            A, X);
+                else
+                    KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit<TARG(ADI), TARG(DRAG), TARG(CART)>), grid, block, P, A, X);
             });
         });
     });
@@ -575,6 +581,12 @@ void launch_particles_normals(int n, const unsigned long long *id, unsigned long
 {
     if (n > 0)
         hipLaunchKernelGGL(k_particles_normals, dim3((n + 255) / 256), dim3(256), 0, st, n, id, seed, step, snv);
+}
+// once per fcpt_run_steps, ahead of its first step and outside any captured graph: *offset + clk->n_hydro_iter is then the
+// Philox counter of every particle launch of the call
+void launch_particles_counter_offset(unsigned long long *offset, unsigned long long counter, const DevClock *clk, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_particles_counter_offset, dim3(1), dim3(1), 0, st, offset, counter, clk);
 }
 
 // rings whose CFL terms read nothing the ghost exchange or the boundary kernels write: ring i reads rows i

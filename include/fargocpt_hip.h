@@ -456,8 +456,9 @@ int fcpt_recalculate_derived(fcpt_ctx *ctx);
  * particles::integrate with ParticleIntegrator: midpoint (integrate_exponential_midpoint, src/particles/
  * particles.cpp:1579-1672, after Zhu et al. 2014 and Mignone et al. 2019) on one radial slab, for the host-stepped
  * loop: per step fcpt_set_bodies, fcpt_particles_step, fcpt_step, fcpt_post -- the particle step reads the gas at the
- * start of the hydro step, where the reference calls it (src/simulation.cpp:177-180).  fcpt_run_steps does not
- * advance particles.  A context that never receives particles launches nothing for them.
+ * start of the hydro step, where the reference calls it (src/simulation.cpp:177-180).  fcpt_run_steps advances
+ * particles only after fcpt_particles_follow_run_steps(ctx, 1), below.  A context that never receives particles launches
+ * nothing for them.
  *
  * Departure from the reference: a particle beyond Rmed[Nr-1] makes the reference read row Nr of a scalar grid (out
  * of bounds); here the lower row of the cell-centred interpolation is clamped to [0, Nr-2] (linear extrapolation
@@ -588,6 +589,28 @@ int fcpt_particles_timestep_init(fcpt_ctx *ctx);
 int fcpt_particles_adaptive_set(fcpt_ctx *ctx, int64_t n, const double *timestep, const double *facold);
 int fcpt_particles_adaptive_get(fcpt_ctx *ctx, int64_t capacity, double *timestep, double *facold, double *r_ddot,
                                 double *phi_ddot, uint32_t *accepted, uint32_t *rejected, int64_t *n);
+
+/* Particles inside fcpt_run_steps.  on = 1: every iteration of fcpt_run_steps on a single slab also takes the particle
+ * step, where the reference has it (src/simulation.cpp:177-180): after the step length of the iteration is in force and
+ * before the gas step, so it reads the gas of the start of the hydro step.  It is the step fcpt_particles_step would
+ * take with dt = the step length the gas step uses, (indirect_x, indirect_y) and the bodies of the last fcpt_set_bodies
+ * and frame_angle = OmegaFrame dt (one rounded product), with the integrator, cartesian, gas_drag and diffusion settings
+ * of the context, and it advances the Philox counter by one.  With snap != 0 fcpt_run_steps calls fcpt_particles_step
+ * itself; with snap = 0 the kernels take dt, frame_angle and the counter from device memory, nothing comes to the host,
+ * and the launch is part of the hipGraph replayed on launch-bound grids (the CFL fold inside the marching source kernel
+ * gives way to the policy launch while particles are present; the gas bits are the same).  A captured graph is replayed
+ * only while the particle launch it holds is the one the context would queue now: whatever fcpt_particles_set,
+ * _diffusion, _integrator, _adaptive_set, _timestep_init, fcpt_set_bodies or this call change in it leads to a new
+ * capture, never to a stale replay (a setting put back before the next fcpt_run_steps changes nothing).  When fcpt_run_steps returns, fcpt_particles_diffusion_get().step has advanced by *nsteps_done, also
+ * when there are no particles.  Guards 1 .. 10 go to the status word and are reported once by the next blocking
+ * particle call, as after fcpt_particles_step.  Bodies do not move inside fcpt_run_steps.
+ * fcpt_run_steps returns FCPT_EINVAL, with *nsteps_done = 0, the clock untouched and nothing queued, while this is on and
+ * the descriptor selects Integrator: Leapfrog, or the explicit integrator is selected and has no step sizes since the
+ * last fcpt_particles_set.
+ * The setting belongs to the context and outlives fcpt_particles_set.  The default is 0: a context that never switches it
+ * on allocates, launches and computes what it did before. */
+int fcpt_particles_follow_run_steps(fcpt_ctx *ctx, int32_t on);
+int fcpt_particles_follow_run_steps_get(const fcpt_ctx *ctx, int32_t *on);
 
 /* The generator itself, on the host (no GPU needed): ten rounds of Philox4x32, and the deviate above. */
 void fcpt_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
