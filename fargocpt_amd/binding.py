@@ -33,6 +33,7 @@ IC_PROFILE, IC_SPREADING_RING, IC_SHOCKTUBE = range(3)
  F_TEMPERATURE, F_POTENTIAL, F_SIGMA0, F_VRAD0, F_VAZI0, F_ENERGY0, F_QPLUS, F_QMINUS,
  F_VISC_CFAC_PHI, F_VISC_CFAC_R, F_MASSFLOW, F_ACCEL_RADIAL, F_ACCEL_AZIMUTHAL) = range(21)
 VECTOR_FIELDS = (F_VRAD, F_VRAD0, F_MASSFLOW, F_ACCEL_RADIAL, F_ACCEL_AZIMUTHAL)
+TABLE_SRC, TABLE_RAD, TABLE_THETA, TABLE_DAMP, TABLE_RING, TABLE_DAMP_RANGES, TABLE_AZIMUTH = range(7)
 COMM_ID_BYTES = 128
 
 ERRORS = {-1: "FCPT_EINVAL", -2: "FCPT_ENOMEM", -3: "FCPT_EHIP", -4: "FCPT_ESPLIT", -5: "FCPT_ENODEV", -6: "FCPT_ESHEAR",
@@ -244,6 +245,16 @@ class Library:
         self.check(f(*args, t.ctypes.data_as(C.POINTER(_i32)), _i32(nt.value), C.byref(nt),
                      s.ctypes.data_as(C.POINTER(_i32)), _i32(ns.value), C.byref(ns)), "selftest_chunk_tables")
         return t, s
+
+    def selftest_ring_tables(self, d: Desc, radii: np.ndarray, table: int) -> np.ndarray:
+        """One of the per-ring tables (TABLE_*) create() would upload for the slab of d.rank, [rows, cols] float64: host logic, no GPU."""
+        rows, cols = _i32(), _i32()
+        f = self.fn("selftest_ring_tables")
+        self.check(f(C.byref(d), _as_dp(radii), _i32(table), None, C.c_int64(0), C.byref(rows), C.byref(cols)), "selftest_ring_tables")
+        out = np.zeros((rows.value, cols.value))
+        self.check(f(C.byref(d), _as_dp(radii), _i32(table), _as_dp(out), C.c_int64(out.size), C.byref(rows), C.byref(cols)),
+                   "selftest_ring_tables")
+        return out
 
     def nbody(self, G: float = 1.0) -> "NBody":
         return NBody(self, G)

@@ -103,50 +103,6 @@ int dev_upload(fcpt_ctx *c, const double **dst, const std::vector<double> &src)
     return FCPT_OK;
 }
 
-// damping.cpp:311-427: which rows a damping call touches and its time scale
-DampRange damp_range(const fcpt_ctx *c, int is_vector, int type, int outer)
-{
-    DampRange r;
-    r.lo = 0;
-    r.hi = -1;
-    r.type = type;
-    r.rlim = r.redge = r.tau = 0;
-    if (!c->d.damping || type == FCPT_DAMP_NONE)
-        return r;
-    const fcpt_desc &d = c->d;
-    const std::vector<double> &radius = is_vector ? c->geo.Rinf : c->geo.Rmed;
-    const int nr = c->s.nr;
-    const int size_radial = is_vector ? nr + 1 : nr;
-    auto clamp = [&](int id) {
-        const int mx = nr - (is_vector ? 0 : 1);
-        return id < 0 ? 0 : (id > mx ? mx : id);
-    };
-    auto omega_k = [&](double rr) { return std::sqrt(d.G * d.hydro_center_mass / (rr * rr * rr)); };
-    if (!outer) {
-        if (!((d.damping_inner_limit > 1.0) && (radius[0] < d.rmin * d.damping_inner_limit)))
-            return r;
-        const double rl = d.rmin * d.damping_inner_limit;
-        const int limit = clamp(is_vector ? rinf_id(d, c->s, c->geo, rl) : rmed_id(d, c->s, c->geo, rl));
-        r.lo = 0;
-        r.hi = limit;
-        r.rlim = rl;
-        r.redge = d.rmin;
-        r.tau = d.damping_time_factor * 2.0 * M_PI / omega_k(d.rmin);
-    } else {
-        if (!((d.damping_outer_limit < 1.0) && (radius[size_radial - 1] > d.rmax * d.damping_outer_limit)))
-            return r;
-        const double rl = d.rmax * d.damping_outer_limit;
-        const int limit =
-            clamp((is_vector ? rinf_id(d, c->s, c->geo, rl) : rmed_id(d, c->s, c->geo, rl)) + 1);
-        r.lo = limit;
-        r.hi = size_radial - 1;
-        r.rlim = rl;
-        r.redge = d.rmax;
-        r.tau = d.damping_time_factor * 2.0 * M_PI / omega_k(d.damping_time_radius_outer);
-    }
-    return r;
-}
-
 // the context's derived switches after its options changed (fcpt_create, fcpt_set_option)
 void apply_options(fcpt_ctx *c, bool at_create = true)
 {
@@ -215,6 +171,161 @@ int copy_initial_values(fcpt_ctx *c)
     return FCPT_OK;
 }
 
+// ---- the device stages of fcpt_create (the host ones: fcpt_tables.cpp) ----
+
+// the geometry and the tables of `t` in device memory, Dev's views of them, and what the context keeps of `t`
+int upload_tables(fcpt_ctx *c, const RingTables &t)
+{
+    Dev &P = c->P;
+    const HostGeometry &g = c->geo;
+    const struct {
+        const double **dst;
+        const std::vector<double> &src;
+    } arrays[] = {{&P.Rmed.p, g.Rmed}, {&P.Rinf.p, g.Rinf}, {&P.Rsup.p, g.Rsup}, {&P.Surf.p, g.Surf}, {&P.InvRmed.p, g.InvRmed},
+                  {&P.InvRinf.p, g.InvRinf}, {&P.InvSurf.p, g.InvSurf}, {&P.InvDiffRmed.p, g.InvDiffRmed},
+                  {&P.InvDiffRsup.p, g.InvDiffRsup}, {&P.InvDiffRsupRb.p, g.InvDiffRsupRb},
+                  {&P.cosphi, t.cosphi}, {&P.sinphi, t.sinphi}, {&P.nu_ring.p, t.nu_ring},
+                  {&P.g_dxtheta.p, t.g_dxtheta}, {&P.g_inv_dxtheta.p, t.g_inv_dxtheta}, {&P.g_dr_invsurf.p, t.g_dr_invsurf},
+                  {&P.g_r_omega.p, t.g_r_omega}, {&P.g_inv_omk.p, t.g_inv_omk}, {&P.g_omk.p, t.g_omk}, {&P.g_ra3.p, t.g_ra3},
+                  {&P.dfac_s.p, t.fs}, {&P.dtau_s.p, t.ts}, {&P.dfac_v.p, t.fv}, {&P.dtau_v.p, t.tv}};
+    for (const auto &a : arrays)
+        if (int rc = dev_upload(c, a.dst, a.src))
+            return rc;
+    if (int rc = dev_upload_raw(c, &c->d_cs_ring, t.cs_ring)) // k_iso_cs_h writes through this pointer, the others read
+        return rc;
+    P.cs_ring.p = c->d_cs_ring;
+    CArrI *const dtype[4] = {&P.dtype_vr, &P.dtype_va, &P.dtype_sig, &P.dtype_e};
+    for (int q = 0; q < 4; ++q)
+        if (int rc = dev_upload_raw(c, &dtype[q]->p, t.dtype[q]))
+            return rc;
+    if (int rc = dev_upload_raw(c, &P.rad_tab, t.rad))
+        return rc;
+    if (int rc = dev_upload_raw(c, &P.theta_tab, t.theta))
+        return rc;
+    if (int rc = dev_upload_raw(c, &P.src_tab, t.src))
+        return rc;
+    if (int rc = dev_upload_raw(c, &P.damp_tab, t.damp_rows))
+        return rc;
+    std::memcpy(c->damp, t.damp, sizeof(c->damp));
+    c->ring_ref_damped = t.ring_ref_damped;
+    c->damp_any = t.damp_any;
+    c->damp_foldable = t.damp_foldable;
+    return FCPT_OK;
+}
+
+// every grid and work array of the slab, zero-filled, and the field table of fcpt_upload / fcpt_download
+int alloc_grids(fcpt_ctx *c)
+{
+    Dev &P = c->P;
+    const fcpt_desc &d = c->d;
+    const int nr = c->s.nr, nphi = d.nphi;
+    const size_t ns = (size_t)nr * nphi, nv = (size_t)(nr + 1) * nphi;
+    P.ring_pstride = nphi / 32 + 4;
+    const struct {
+        double **p;
+        size_t n;
+    } grids[] = {{&P.sigma, ns}, {&P.vrad, nv}, {&P.vazi, ns}, {&P.energy, ns}, {&P.vrad_b, nv}, {&P.vazi_b, ns}, {&P.energy_b, ns},
+                 {&P.pressure, ns}, {&P.soundspeed, ns}, {&P.scale_height, ns}, {&P.viscosity, ns}, {&P.temperature, ns},
+                 {&P.potential, ns},
+                 {&P.sigma0, ns}, {&P.vrad0, nv}, {&P.vazi0, ns}, {&P.energy0, ns},
+                 {&P.qr, ns}, {&P.qphi, ns}, {&P.divv, ns}, {&P.trr, ns}, {&P.tpp, ns}, {&P.trp, nv}, {&P.qplus, ns}, {&P.qminus, ns},
+                 {&P.rmpA, ns}, {&P.rmmA, ns}, {&P.lpA, ns}, {&P.lmA, ns}, {&P.sigA, ns}, {&P.eA, ns},
+                 {&P.rmpB, ns}, {&P.rmmB, ns}, {&P.lpB, ns}, {&P.lmB, ns}, {&P.sigB, ns}, {&P.eB, ns},
+                 {&P.vmean, (size_t)nr + 1}, {&P.vconst, (size_t)nr},
+                 {&P.cfl_part, (size_t)(nr + 256) * (size_t)((nphi + 255) / 256 + 1)}, {&P.ring_part, (size_t)nr * P.ring_pstride},
+                 // null unless StabilizeViscosity / WriteMassFlow / BodyForceFromPotential: no / the ideal EOS
+                 {&P.cfac_phi, d.stabilize_viscosity ? ns : 0}, {&P.cfac_r, d.stabilize_viscosity ? ns : 0},
+                 {&P.massflow, d.write_massflow ? nv : 0},
+                 // (zero-filled: rows 0 and nr are never written, Pframeforce.cpp:121-123)
+                 {&P.accel_r, d.body_force_from_potential ? 0 : nv}, {&P.accel_az, d.body_force_from_potential ? 0 : nv},
+                 {&P.qdiff, d.eos == FCPT_EOS_IDEAL ? ns : 0}};
+    for (const auto &g : grids)
+        if (g.n)
+            if (int rc = dev_alloc(c, g.p, g.n))
+                return rc;
+    if (int rc = dev_alloc(c, &P.nshift, (size_t)nr))
+        return rc;
+    if (int rc = dev_alloc(c, &P.clk, 1))
+        return rc;
+    if (int rc = dev_alloc(c, &P.shift_jump, 8))
+        return rc;
+    if (int rc = dev_alloc(c, &P.shift_tab, (size_t)nr))
+        return rc;
+    c->tf_sched_cap = (size_t)4 * 65536; // graded chunks: two to three rounds of a 512-CU device's wavefront slots, and the padding
+    if (int rc = dev_alloc(c, &c->tf_sched_dev, c->tf_sched_cap))
+        return rc;
+    c->sm_sched_cap = (size_t)4 * (8 * 4 * 8 * 64 + 64); // one entry per wavefront slot of a 512-CU device at 8 per SIMD
+    if (int rc = dev_alloc(c, &c->sm_sched_dev, c->sm_sched_cap))
+        return rc;
+    if (hipHostMalloc((void **)&c->h_clk, sizeof(DevClock)) != hipSuccess) {
+        set_error("hipHostMalloc failed");
+        return FCPT_ENOMEM;
+    }
+    P.vmean_c.p = P.vmean;
+    P.vconst_c.p = P.vconst;
+    P.nshift_c.p = P.nshift;
+    c->grid[FCPT_F_SIGMA] = P.sigma;
+    c->grid[FCPT_F_VRAD] = P.vrad;
+    c->grid[FCPT_F_VAZI] = P.vazi;
+    c->grid[FCPT_F_ENERGY] = P.energy;
+    c->grid[FCPT_F_PRESSURE] = P.pressure;
+    c->grid[FCPT_F_SOUNDSPEED] = P.soundspeed;
+    c->grid[FCPT_F_SCALE_HEIGHT] = P.scale_height;
+    c->grid[FCPT_F_VISCOSITY] = P.viscosity;
+    c->grid[FCPT_F_TEMPERATURE] = P.temperature;
+    c->grid[FCPT_F_POTENTIAL] = P.potential;
+    c->grid[FCPT_F_SIGMA0] = P.sigma0;
+    c->grid[FCPT_F_VRAD0] = P.vrad0;
+    c->grid[FCPT_F_VAZI0] = P.vazi0;
+    c->grid[FCPT_F_ENERGY0] = P.energy0;
+    c->grid[FCPT_F_QPLUS] = P.qplus;
+    c->grid[FCPT_F_QMINUS] = P.qminus;
+    c->grid[FCPT_F_VISC_CFAC_PHI] = P.cfac_phi; // null unless StabilizeViscosity
+    c->grid[FCPT_F_VISC_CFAC_R] = P.cfac_r;
+    c->grid[FCPT_F_MASSFLOW] = P.massflow; // null unless WriteMassFlow
+    c->grid[FCPT_F_ACCEL_RADIAL] = P.accel_r; // null unless BodyForceFromPotential: no
+    c->grid[FCPT_F_ACCEL_AZIMUTHAL] = P.accel_az;
+    return FCPT_OK;
+}
+
+// FCPT_TF_SCHEDULE of tuning runs: "28x56,12x24,6" = 56 chunks of 28 rings, 24 of 12, the rest of 6
+std::vector<int> parse_tf_schedule(const char *q, int nr)
+{
+    std::vector<int> lengths;
+    while (*q) {
+        char *e = nullptr;
+        const long a = strtol(q, &e, 10);
+        if (e == q)
+            break;
+        long n = 1;
+        q = e;
+        if (*q == 'x' || *q == 'X') {
+            n = strtol(q + 1, &e, 10);
+            q = e;
+        }
+        for (long k = 0; k < n && (long)lengths.size() < 4l * nr; ++k)
+            lengths.push_back((int)(a < 1 ? 1 : a));
+        while (*q == ',' || *q == ' ')
+            ++q;
+    }
+    return lengths;
+}
+
+int seed_clock(fcpt_ctx *c)
+{
+    DevClock clk;
+    std::memset(&clk, 0, sizeof(clk));
+    clk.last_dt = c->d.first_dt; // Interpret.cpp:86
+    clk.dt = c->d.first_dt;
+    clk.dt_min = 1.0e300;
+    clk.dt_max = 0.0;
+    if (hipMemcpy(c->P.clk, &clk, sizeof(clk), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("hipMemcpy of the clock failed");
+        return FCPT_EHIP;
+    }
+    return FCPT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -249,33 +360,12 @@ int fcpt_set_device(int32_t device)
 
 int fcpt_create(const fcpt_desc *d, const double *radii, fcpt_ctx **out)
 {
-    if (!d || !radii || !out) {
+    if (!out) {
         set_error("null argument");
         return FCPT_EINVAL;
     }
-    if (d->struct_size != sizeof(fcpt_desc) || d->abi_version != FCPT_ABI_VERSION) {
-        set_error("descriptor ABI mismatch: size %u (expected %zu), version %u (expected %d)", d->struct_size,
-                  sizeof(fcpt_desc), d->abi_version, FCPT_ABI_VERSION);
-        return FCPT_EINVAL;
-    }
-    if (d->stabilize_viscosity < 0 || d->stabilize_viscosity > 2) {
-        set_error("StabilizeViscosity must be 0, 1 or 2");
-        return FCPT_EINVAL;
-    }
-    if (d->cooling_surface && d->eos == FCPT_EOS_IDEAL && (d->opacity < FCPT_OPACITY_LIN || d->opacity > FCPT_OPACITY_SIMPLE)) {
-        set_error("Opacity: Lin, Bell, Constant and Simple are the laws of the path (src/opacity.cpp:10-43)");
-        return FCPT_EINVAL;
-    }
-    // the exponential spacing's Newton iteration (init.cpp:113-131) collapses to NaN for coarse grids
-    for (int i = 0; d->nr_global >= 1 && i <= d->nr_global + FCPT_GEOM_PAD; ++i)
-        if (!std::isfinite(radii[i]) || radii[i] <= 0.0 || (i > 0 && !(radii[i] > radii[i - 1]))) {
-            set_error("radii[%d] = %g: the interfaces must be finite, positive and strictly increasing", i, radii[i]);
-            return FCPT_EINVAL;
-        }
-    if ((long long)(d->nr_global + 1) * (long long)d->nphi >= (1ll << 31)) {
-        set_error("grid too large for 32-bit cell indices");
-        return FCPT_EINVAL;
-    }
+    if (int rc = validate_create(d, radii))
+        return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device available: the HIP path cannot run (there is no CPU fallback)");
@@ -284,443 +374,31 @@ int fcpt_create(const fcpt_desc *d, const double *radii, fcpt_ctx **out)
     fcpt_ctx *c = new (std::nothrow) fcpt_ctx();
     if (!c)
         return FCPT_ENOMEM;
+    std::memset(&c->P, 0, sizeof(c->P)); // (padding too: the hipGraph replay compares Dev views with memcmp)
     c->d = *d;
     if (d->eos != FCPT_EOS_IDEAL) // no energy equation: SubStep3 and with it every cooling term is not called
         c->d.cooling_surface = c->d.cooling_beta = 0; // (simulation.cpp:205-207 `if (parameters::Adiabatic)`)
-    d = &c->d;
     (void)hipGetDevice(&c->device);
-    if (int rc = split_domain(*d, c->s)) {
-        delete c;
-        return rc;
-    }
-    const int nr = c->s.nr, nphi = d->nphi;
-    c->radii.assign(radii, radii + d->nr_global + FCPT_GEOM_PAD + 1);
-    build_geometry(*d, c->s, radii, c->geo);
-
-    Dev &P = c->P;
-    std::memset(&P, 0, sizeof(P));
-    P.nr = nr;
-    P.nphi = nphi;
-    P.dphi = c->geo.dphi;
-    P.invdphi = c->geo.invdphi;
-    int rc = FCPT_OK;
-#define UP(field) \
-    if (!rc)      \
-        rc = dev_upload(c, &P.field.p, c->geo.field);
-    UP(Rmed) UP(Rinf) UP(Rsup) UP(Surf) UP(InvRmed) UP(InvRinf) UP(InvSurf) UP(InvDiffRmed)
-    UP(InvDiffRsup) UP(InvDiffRsupRb)
-#undef UP
-    std::vector<double> cp(nphi), sp(nphi), cs_ring(nr);
-    for (int j = 0; j < nphi; ++j) { // SideEuler.cpp:60-63
-        cp[j] = std::cos(c->geo.dphi * (double)j);
-        sp[j] = std::sin(c->geo.dphi * (double)j);
-    }
-    for (int i = 0; i < nr; ++i) { // SourceEuler.cpp:1080-1088
-        const double vK = std::sqrt(d->G * d->hydro_center_mass / c->geo.Rmed[i]);
-        const double h = d->aspect_ratio * std::pow(c->geo.Rmed[i], d->flaring_index);
-        cs_ring[i] = h * vK;
+    int rc = split_domain(c->d, c->s);
+    if (!rc) {
+        c->radii.assign(radii, radii + d->nr_global + FCPT_GEOM_PAD + 1);
+        build_geometry(c->d, c->s, radii, c->geo);
+        RingTables tables;
+        build_ring_tables(c->d, c->s, c->geo, tables);
+        rc = upload_tables(c, tables);
     }
     if (!rc)
-        rc = dev_upload(c, &P.cosphi, cp);
-    if (!rc)
-        rc = dev_upload(c, &P.sinphi, sp);
-    const double *csr = nullptr;
-    if (!rc)
-        rc = dev_upload(c, &csr, cs_ring);
-    c->d_cs_ring = const_cast<double *>(csr);
-    P.cs_ring.p = csr;
-    {
-        const HostGeometry &g = c->geo;
-        std::vector<double> a(nr + 1, 0.0), b(nr + 1, 0.0), c2(nr + 1, 0.0), d2(nr + 1, 0.0), e2(nr + 1, 0.0);
-        for (int i = 0; i <= nr; ++i) {
-            a[i] = 2.0 / (g.dphi * (g.Rsup[i] + g.Rinf[i]));
-            b[i] = 1.0 / (g.Rsup[i] + g.Rinf[i]);
-            d2[i] = 1.0 / (g.Rinf[i + 1] * g.Rinf[i + 1] - g.Rinf[i] * g.Rinf[i]);
-            if (i >= 1) {
-                c2[i] = 1.0 / (g.Rmed[i] * g.Rmed[i] - g.Rmed[i - 1] * g.Rmed[i - 1]);
-                e2[i] = 1.0 / (g.Rmed[i] + g.Rmed[i - 1]);
-            }
-        }
-        if (!rc) rc = dev_upload(c, &P.g_inv_dxt_src.p, a);
-        if (!rc) rc = dev_upload(c, &P.g_inv_rsum.p, b);
-        if (!rc) rc = dev_upload(c, &P.g_inv_drmed2.p, c2);
-        if (!rc) rc = dev_upload(c, &P.g_inv_dra2.p, d2);
-        if (!rc) rc = dev_upload(c, &P.g_inv_rmsum.p, e2);
-        std::vector<double> t1(nr + 1, 0.0), t2(nr + 1, 0.0), t3(nr + 1, 0.0), t4(nr + 1, 0.0);
-        for (int i = 0; i < nr; ++i) {
-            t1[i] = g.dphi * g.Rmed[i];
-            t2[i] = 1.0 / t1[i];
-            t3[i] = (g.Rsup[i] - g.Rinf[i]) * g.InvSurf[i];
-            t4[i] = g.Rmed[i] * d->omega_frame;
-        }
-        if (!rc) rc = dev_upload(c, &P.g_dxtheta.p, t1);
-        if (!rc) rc = dev_upload(c, &P.g_inv_dxtheta.p, t2);
-        if (!rc) rc = dev_upload(c, &P.g_dr_invsurf.p, t3);
-        if (!rc) rc = dev_upload(c, &P.g_r_omega.p, t4);
-        std::vector<double> t5(nr + 1, 0.0);
-        for (int i = 0; i < nr; ++i) {
-            const double rm = g.Rmed[i];
-            t5[i] = 1.0 / std::sqrt(d->G * d->hydro_center_mass / (rm * rm * rm));
-        }
-        if (!rc) rc = dev_upload(c, &P.g_inv_omk.p, t5);
-        std::vector<double> t6(nr + 1, 0.0);
-        for (int i = 0; i < nr; ++i) {
-            const double rm = g.Rmed[i];
-            t6[i] = std::sqrt(d->G * d->hydro_center_mass / (rm * rm * rm));
-        }
-        if (!rc) rc = dev_upload(c, &P.g_omk.p, t6);
-        std::vector<double> t7(nr + 2, 0.0);
-        for (int i = 0; i <= nr; ++i)
-            t7[i] = std::pow(g.Rinf[i], 3);
-        if (!rc) rc = dev_upload(c, &P.g_ra3.p, t7);
-        std::vector<RadRow> rt(nr + 2);
-        for (int k = -1; k <= nr; ++k) {
-            const bool open = k > 0 && k < nr;
-            const int kk = open ? k : 1;
-            RadRow &r = rt[k + 1];
-            r.dr_lo = g.Rmed[kk] - g.Rmed[kk - 1];
-            r.dr_hi = g.Rmed[kk + 1] - g.Rmed[kk];
-            r.gphi = g.dphi * g.Rinf[kk];
-            r.idr_up = (k + 1 >= 1 && k + 1 <= nr - 1) ? g.InvDiffRmed[k + 1] : 0.0;
-        }
-        std::vector<ThetaRow> tt(nr);
-        for (int i = 0; i < nr; ++i)
-            tt[i] = ThetaRow{g.InvSurf[i], t1[i], t2[i], t3[i], g.InvRmed[i], t4[i], g.Rmed[i], 0.0};
-        if (!rc) rc = dev_upload_raw(c, &P.rad_tab, rt);
-        if (!rc) rc = dev_upload_raw(c, &P.theta_tab, tt);
-        if (!rc) rc = dev_alloc(c, &P.shift_tab, (size_t)nr);
-    }
-    std::vector<double> nu_ring(nr);
-    {
-        // isothermal alpha viscosity per ring, exactly as k_iso_cs_h + k_viscosity evaluate it:
-        // H = cs * (1 / Omega_K), nu = alpha * H * cs
-        for (int i = 0; i < nr; ++i) {
-            const double r = c->geo.Rmed[i];
-            const double inv_omega_kepler = 1.0 / std::sqrt(d->G * d->hydro_center_mass / (r * r * r));
-            const double H = cs_ring[i] * inv_omega_kepler;
-            nu_ring[i] = d->viscous_alpha * H * cs_ring[i];
-        }
-        if (!rc)
-            rc = dev_upload(c, &P.nu_ring.p, nu_ring);
-    }
-    {
-        // per-iteration rows of the marching source kernel (k_source_march): every per-ring factor
-        // with the index expression and operation order of the kernel's former array reads
-        const HostGeometry &g = c->geo;
-        auto at = [](const std::vector<double> &v, int i) { return (i >= 0 && i < (int)v.size()) ? v[i] : 0.0; };
-        auto crow = [nr](int r) { return r < 0 ? 0 : (r > nr - 1 ? nr - 1 : r); };
-        const bool alpha = d->viscous_alpha > 0;
-        auto nu_of = [&](int r) { return alpha ? nu_ring[crow(r)] : d->constant_viscosity; };
-        const double C2 = d->artificial_viscosity_factor * d->artificial_viscosity_factor;
-        std::vector<SrcRow> rows(nr + 8);
-        for (int m = -2; m <= nr + 5; ++m) {
-            SrcRow &R = rows[m + 2];
-            std::memset(&R, 0, sizeof(R));
-            {
-                const int rc0 = crow(m), rc1 = crow(m - 1);
-                R.cs2_m = cs_ring[rc0] * cs_ring[rc0];
-                R.cs2_m1 = cs_ring[rc1] * cs_ring[rc1];
-                R.idr_m = at(g.InvDiffRmed, m);
-                R.rinf_om_m = at(g.Rinf, m) * d->omega_frame;
-                R.inv_rinf_m = at(g.InvRinf, m);
-                R.inv_dxt_m = (m >= 0 && m <= nr) ? 2.0 / (g.dphi * (g.Rsup[m] + g.Rinf[m])) : 0.0;
-            }
-            {
-                const int r = crow(m - 1);
-                R.inv_drsup_b = g.InvDiffRsup[r];
-                R.inv_rmed_b = g.InvRmed[r];
-                const double Dr = g.Rinf[r + 1] - g.Rinf[r];
-                const double rDphi = g.Rmed[r] * g.dphi;
-                const double dx = nphi <= 16 ? std::min(Dr, rDphi) : std::max(Dr, rDphi);
-                R.lsq_b = C2 * (dx * dx);
-                R.rinf_b1 = g.Rinf[r + 1];
-                R.rinf_b0 = g.Rinf[r];
-                R.inv_drsuprb_b = g.InvDiffRsupRb[r];
-                const double rm = g.Rmed[r];
-                R.inv_omk_b = 1.0 / std::sqrt(d->G * d->hydro_center_mass / (rm * rm * rm));
-                R.inv_dxtheta_b = 1.0 / (g.dphi * rm);
-            }
-            {
-                const int r = m - 1;
-                if (r >= 1 && r <= nr) {
-                    R.inv_rsum_c = 1.0 / (g.Rsup[r] + g.Rinf[r]);
-                    R.rmed_c = g.Rmed[r];
-                    R.rmed_cm1 = g.Rmed[r - 1];
-                    R.inv_drmed2_c = 1.0 / (g.Rmed[r] * g.Rmed[r] - g.Rmed[r - 1] * g.Rmed[r - 1]);
-                }
-                R.idr_c = at(g.InvDiffRmed, r);
-                R.inv_dxtheta_c = at(g.InvRmed, r) * g.invdphi;
-            }
-            {
-                const int r = crow(m - 2);
-                R.rinf_d1 = g.Rinf[r + 1];
-                R.rinf_d0 = g.Rinf[r];
-                R.inv_drsuprb_d = g.InvDiffRsupRb[r];
-                R.inv_rmed_d = g.InvRmed[r];
-                R.inv_drsup_d = g.InvDiffRsup[r];
-                R.nu_d = nu_of(m - 2);
-            }
-            {
-                const int r = m - 1;
-                if (r >= 1 && r <= nr - 1) {
-                    R.inv_rmed_r = g.InvRmed[r];
-                    R.inv_rmed_rm1 = g.InvRmed[r - 1];
-                    R.idr_r = g.InvDiffRmed[r];
-                    R.rinf_r = g.Rinf[r];
-                    R.inv_rinf_r = g.InvRinf[r];
-                    const double nu1 = nu_of(r), nu2 = nu_of(r - 1);
-                    R.nu_avg_r = 0.25 * (nu1 + nu2 + nu1 + nu2);
-                }
-            }
-            {
-                const int k = m - 2;
-                if (k >= 1 && k <= nr) {
-                    const double ra1 = at(g.Rinf, k + 1), ra0 = g.Rinf[k];
-                    R.inv_rmed_k = at(g.InvRmed, k);
-                    R.two_inv_dra2_k = 2.0 * (1.0 / (ra1 * ra1 - ra0 * ra0));
-                    R.ra1sq_k = ra1 * ra1;
-                    R.ra0sq_k = ra0 * ra0;
-                    R.inv_rmsum_k = 1.0 / (g.Rmed[k] + g.Rmed[k - 1]);
-                    R.rmed_k = g.Rmed[k];
-                    R.rmed_km1 = g.Rmed[k - 1];
-                    R.idr_k = at(g.InvDiffRmed, k);
-                }
-            }
-        }
-        if (!rc) rc = dev_upload_raw(c, &P.src_tab, rows);
-    }
-
-    const size_t ns = (size_t)nr * nphi, nv = (size_t)(nr + 1) * nphi;
-#define AL(field, n) \
-    if (!rc)         \
-        rc = dev_alloc(c, &P.field, (n));
-    AL(sigma, ns) AL(vrad, nv) AL(vazi, ns) AL(energy, ns) AL(vrad_b, nv) AL(vazi_b, ns) AL(energy_b, ns)
-    AL(pressure, ns) AL(soundspeed, ns) AL(scale_height, ns) AL(viscosity, ns) AL(temperature, ns)
-    AL(potential, ns)
-    AL(sigma0, ns) AL(vrad0, nv) AL(vazi0, ns) AL(energy0, ns)
-    AL(qr, ns) AL(qphi, ns) AL(divv, ns) AL(trr, ns) AL(tpp, ns) AL(trp, nv) AL(qplus, ns) AL(qminus, ns)
-    AL(rmpA, ns) AL(rmmA, ns) AL(lpA, ns) AL(lmA, ns) AL(sigA, ns) AL(eA, ns)
-    AL(rmpB, ns) AL(rmmB, ns) AL(lpB, ns) AL(lmB, ns) AL(sigB, ns) AL(eB, ns)
-    AL(vmean, (size_t)nr + 1) AL(vconst, (size_t)nr) AL(nshift, (size_t)nr) AL(clk, 1) AL(shift_jump, 8)
-    AL(cfl_part, (size_t)(nr + 256) * (size_t)((nphi + 255) / 256 + 1))
-    P.ring_pstride = nphi / 32 + 4;
-    AL(ring_part, (size_t)nr * P.ring_pstride)
-    P.stabilize = d->stabilize_viscosity;
-    if (P.stabilize) {
-        AL(cfac_phi, ns) AL(cfac_r, ns)
-    }
-    if (d->write_massflow) {
-        AL(massflow, nv)
-    }
-    P.accel_force = d->body_force_from_potential ? 0 : 1;
-    if (P.accel_force) {
-        AL(accel_r, nv) AL(accel_az, nv) // zero-filled: rows 0 and nr are never written (Pframeforce.cpp:121-123)
-    }
-    if (!rc && d->eos == FCPT_EOS_IDEAL)
-        rc = dev_alloc(c, &P.qdiff, ns);
-#undef AL
-    if (!rc && hipHostMalloc((void **)&c->h_clk, sizeof(DevClock)) != hipSuccess) {
-        set_error("hipHostMalloc failed");
-        rc = FCPT_ENOMEM;
+        rc = alloc_grids(c);
+    if (!rc) {
+        fill_parameters(c->d, c->s, c->geo, c->P);
+        rc = seed_clock(c);
     }
     if (rc) {
         fcpt_destroy(c);
         return rc;
     }
-    P.vmean_c.p = P.vmean;
-    P.vconst_c.p = P.vconst;
-    P.nshift_c.p = P.nshift;
-    c->grid[FCPT_F_SIGMA] = P.sigma;
-    c->grid[FCPT_F_VRAD] = P.vrad;
-    c->grid[FCPT_F_VAZI] = P.vazi;
-    c->grid[FCPT_F_ENERGY] = P.energy;
-    c->grid[FCPT_F_PRESSURE] = P.pressure;
-    c->grid[FCPT_F_SOUNDSPEED] = P.soundspeed;
-    c->grid[FCPT_F_SCALE_HEIGHT] = P.scale_height;
-    c->grid[FCPT_F_VISCOSITY] = P.viscosity;
-    c->grid[FCPT_F_TEMPERATURE] = P.temperature;
-    c->grid[FCPT_F_POTENTIAL] = P.potential;
-    c->grid[FCPT_F_SIGMA0] = P.sigma0;
-    c->grid[FCPT_F_VRAD0] = P.vrad0;
-    c->grid[FCPT_F_VAZI0] = P.vazi0;
-    c->grid[FCPT_F_ENERGY0] = P.energy0;
-    c->grid[FCPT_F_QPLUS] = P.qplus;
-    c->grid[FCPT_F_QMINUS] = P.qminus;
-    c->grid[FCPT_F_VISC_CFAC_PHI] = P.cfac_phi; // null unless StabilizeViscosity
-    c->grid[FCPT_F_VISC_CFAC_R] = P.cfac_r;
-    c->grid[FCPT_F_MASSFLOW] = P.massflow; // null unless WriteMassFlow
-    c->grid[FCPT_F_ACCEL_RADIAL] = P.accel_r; // null unless BodyForceFromPotential: no
-    c->grid[FCPT_F_ACCEL_AZIMUTHAL] = P.accel_az;
-
-    P.zero_no_ghost = c->s.zero_no_ghost;
-    P.one_no_ghost_vr = c->s.one_no_ghost_vr;
-    P.max_no_ghost = c->s.max_no_ghost;
-    P.maxmo_no_ghost_vr = c->s.maxmo_no_ghost_vr;
-    P.first_active = c->s.radial_first_active;
-    P.active_size = c->s.radial_active_size;
-    P.is_first = c->s.is_first;
-    P.is_last = c->s.is_last;
-    P.adiabatic = d->eos == FCPT_EOS_IDEAL;
-    P.art_visc = d->artificial_viscosity;
-    P.art_visc_dissipation = d->artificial_viscosity_dissipation;
-    P.heating_viscous = d->heating_viscous;
-    P.fast_transport = d->fast_transport;
-    P.limiter = d->flux_limiter;
-    P.leapfrog = d->integrator == FCPT_INTEGRATOR_LEAPFROG;
-    P.alpha_viscosity = d->viscous_alpha > 0;
-    P.gamma = d->adiabatic_index;
-    P.mu = d->mu;
-    P.Rgas = d->Rgas;
-    P.G = d->G;
-    P.Mc = d->hydro_center_mass;
-    P.sigma_sb = d->sigma_sb;
-    P.c_light = d->c_light;
-    P.aspect_ratio = d->aspect_ratio;
-    P.flaring_index = d->flaring_index;
-    P.tmin = d->minimum_temperature;
-    P.cooling_surface = d->cooling_surface;
-    P.opacity = d->opacity;
-    P.cooling_beta = d->cooling_beta;
-    P.cooling_beta_reference = d->cooling_beta_reference;
-    P.cooling_radiative_factor = d->cooling_radiative_factor;
-    P.kappa_const = d->kappa_const;
-    P.kappa_factor = d->kappa_factor;
-    P.tau_factor = d->tau_factor;
-    P.tau_min = d->tau_min;
-    P.density_factor = d->density_factor;
-    P.cooling_beta_value = d->cooling_beta_value;
-    P.cooling_beta_ramp_up = d->cooling_beta_ramp_up;
-    P.temperature_cgs = d->temperature_cgs;
-    P.density_cgs = d->density_cgs;
-    P.opacity_cgs = d->opacity_cgs;
-    P.emin_fac = d->minimum_temperature / d->mu * d->Rgas / (d->adiabatic_index - 1.0);
-    P.emax_fac = d->maximum_temperature / d->mu * d->Rgas / (d->adiabatic_index - 1.0);
-    P.b_fac = d->mu * (d->adiabatic_index - 1.0) / d->Rgas;
-    P.alpha_fac = 2.0 * 4.0 * d->sigma_sb / d->c_light;
-    P.tmax = d->maximum_temperature;
-    P.sigma_floor_abs = d->sigma_floor * d->sigma0;
-    P.sigma_floor_rel = d->sigma_floor;
-    P.sigma0_val = d->sigma0;
-    P.alpha = d->viscous_alpha;
-    P.nu_const = d->constant_viscosity;
-    P.radial_viscosity_factor = d->radial_viscosity_factor;
-    P.art_visc_factor = d->artificial_viscosity_factor;
-    P.heating_viscous_factor = d->heating_viscous_factor;
-    P.omega_frame = d->omega_frame;
-    P.thickness_smoothing = d->thickness_smoothing;
-    P.cfl = d->cfl;
-    P.cfl_max_var = d->cfl_max_var;
-    P.heating_cooling_cfl_limit = d->heating_cooling_cfl_limit;
-    P.monitor_timestep = d->monitor_timestep;
-    for (int k = 0; k < 2; ++k) {
-        P.bc_sigma[k] = d->bc_sigma[k];
-        P.bc_energy[k] = d->bc_energy[k];
-        P.bc_vrad[k] = d->bc_vrad[k];
-        P.bc_vaz[k] = d->bc_vaz[k];
-        P.kep_vaz[k] = d->keplerian_vaz_factor[k];
-        P.kep_vrad[k] = d->keplerian_vrad_factor[k];
-    }
-    // default body: the central star at the origin
-    P.nbodies = 1;
-    P.bm[0] = d->hydro_center_mass;
-
-    const int dtype[4][2] = {{d->damp_vrad[0], d->damp_vrad[1]},
-                             {d->damp_vaz[0], d->damp_vaz[1]},
-                             {d->damp_sigma[0], d->damp_sigma[1]},
-                             {d->damp_energy[0], d->damp_energy[1]}};
-    for (int q = 0; q < 4; ++q)
-        for (int o = 0; o < 2; ++o)
-            c->damp[q][o] = damp_range(c, q == 0, dtype[q][o], o);
-
-    {
-        // per-ring damping tables for the fused end-of-transport kernel (reference / zero targets;
-        // "mean" needs a ring reduction and keeps the separate k_damping launches)
-        std::vector<double> fs(nr + 1, 0.0), ts(nr + 1, 1.0), fv(nr + 1, 0.0), tv(nr + 1, 1.0);
-        std::vector<int> ty[4];
-        bool any = false, mean = false;
-        for (int q = 0; q < 4; ++q) {
-            ty[q].assign(nr + 1, 0);
-            for (int o = 0; o < 2; ++o) {
-                const DampRange &r = c->damp[q][o];
-                if (r.type == FCPT_DAMP_NONE || r.lo > r.hi)
-                    continue;
-                any = true;
-                mean = mean || r.type == FCPT_DAMP_MEAN;
-                const std::vector<double> &radius = q == 0 ? c->geo.Rinf : c->geo.Rmed;
-                for (int i = r.lo; i <= r.hi; ++i) {
-                    const double t = (radius[i] - r.rlim) / (r.redge - r.rlim);
-                    (q == 0 ? fv : fs)[i] = t * t;
-                    (q == 0 ? tv : ts)[i] = r.tau;
-                    ty[q][i] = r.type == FCPT_DAMP_REFERENCE ? 1 : 2;
-                }
-            }
-        }
-        auto upi = [&](CArrI &dst, const std::vector<int> &src) {
-            int *p = nullptr;
-            if (int e = dev_alloc(c, &p, src.size()))
-                return e;
-            if (hipMemcpy(p, src.data(), src.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-                return (int)FCPT_EHIP;
-            dst.p = p;
-            return (int)FCPT_OK;
-        };
-        if (!rc) rc = dev_upload(c, &P.dfac_s.p, fs);
-        if (!rc) rc = dev_upload(c, &P.dtau_s.p, ts);
-        if (!rc) rc = dev_upload(c, &P.dfac_v.p, fv);
-        if (!rc) rc = dev_upload(c, &P.dtau_v.p, tv);
-        if (!rc) rc = upi(P.dtype_vr, ty[0]);
-        if (!rc) rc = upi(P.dtype_va, ty[1]);
-        if (!rc) rc = upi(P.dtype_sig, ty[2]);
-        if (!rc) rc = upi(P.dtype_e, ty[3]);
-        std::vector<DampRow> dr(nr + 1);
-        for (int i = 0; i <= nr; ++i)
-            dr[i] = DampRow{fs[i], ts[i], fv[i], tv[i], ty[0][i], ty[1][i], ty[2][i], ty[3][i], {0.0, 0.0}};
-        if (!rc) rc = dev_upload_raw(c, &P.damp_tab, dr);
-        c->ring_ref_damped.assign(nr, 0);
-        for (int i = 0; i < nr; ++i)
-            c->ring_ref_damped[i] = (ty[0][i] == 1 || ty[1][i] == 1 || ty[2][i] == 1 || ty[3][i] == 1) ? 1 : 0;
-        c->tf_sched_cap = (size_t)4 * 65536; // graded chunks: two to three rounds of a 512-CU device's wavefront slots, and the padding
-        if (!rc) rc = dev_alloc(c, &c->tf_sched_dev, c->tf_sched_cap);
-        c->sm_sched_cap = (size_t)4 * (8 * 4 * 8 * 64 + 64); // one entry per wavefront slot of a 512-CU device at 8 per SIMD
-        if (!rc) rc = dev_alloc(c, &c->sm_sched_dev, c->sm_sched_cap);
-        if (const char *q = getenv("FCPT_TF_SCHEDULE")) { // tuning runs: "28x56,12x24,6" = 56 chunks of 28 rings, 24 of 12, the rest of 6
-            while (*q) {
-                char *e = nullptr;
-                const long a = strtol(q, &e, 10);
-                if (e == q)
-                    break;
-                long n = 1;
-                q = e;
-                if (*q == 'x' || *q == 'X') {
-                    n = strtol(q + 1, &e, 10);
-                    q = e;
-                }
-                for (long k = 0; k < n && (long)c->tf_lengths.size() < 4l * nr; ++k)
-                    c->tf_lengths.push_back((int)(a < 1 ? 1 : a));
-                while (*q == ',' || *q == ' ')
-                    ++q;
-            }
-        }
-        if (rc) {
-            fcpt_destroy(c);
-            return rc;
-        }
-        // leapfrog kicks the gas once more after the transport, so its damping cannot be folded in
-        c->damp_any = d->damping && any;
-        c->damp_foldable = d->damping && any && !mean && d->integrator == FCPT_INTEGRATOR_EULER;
-    }
-
-    DevClock clk;
-    std::memset(&clk, 0, sizeof(clk));
-    clk.last_dt = d->first_dt; // Interpret.cpp:86
-    clk.dt = d->first_dt;
-    clk.dt_min = 1.0e300;
-    clk.dt_max = 0.0;
-    if (hipMemcpy(P.clk, &clk, sizeof(clk), hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("hipMemcpy of the clock failed");
-        fcpt_destroy(c);
-        return FCPT_EHIP;
-    }
+    if (const char *q = getenv("FCPT_TF_SCHEDULE"))
+        c->tf_lengths = parse_tf_schedule(q, c->s.nr);
     options_from_environment(c->P.opt);
     apply_options(c);
     *out = c;

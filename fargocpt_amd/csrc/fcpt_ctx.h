@@ -1,5 +1,6 @@
 // Shared by the translation units of the device side of the C ABI: the context structure and the helpers that more
-// than one of them uses.  fcpt_context.hip: creation, options, transfers, initial physics, profiling;
+// than one of them uses.  fcpt_context.hip: creation (the device stages: uploads, grids, clock -- what it uploads is
+// built by the host unit fcpt_tables.cpp, declared in fcpt_internal.h), options, transfers, initial physics, profiling;
 // fcpt_step.hip: CFL, the step, the final boundary call, the run loop (+ hipGraph replay);
 // fcpt_exchange.hip: ghost exchange and the RCCL entry points; fcpt_particles.hip: dust particles.
 #ifndef FCPT_CTX_H
@@ -18,7 +19,7 @@
 #include "fcpt_comm.h"
 #include "fcpt_kernels.h"
 
-using namespace fcpt; // private header of three translation units of namespace-fcpt code around one C struct
+using namespace fcpt; // private header of four translation units of namespace-fcpt code around one C struct
 
 #define HIPCHK(call)                                                                        \
     do {                                                                                    \
@@ -172,7 +173,7 @@ template <class T> int dev_alloc(fcpt_ctx *c, T **p, size_t n)
     return FCPT_OK;
 }
 
-template <class T> int dev_upload_raw(fcpt_ctx *c, const T **dst, const std::vector<T> &src)
+template <class T, class D> int dev_upload_raw(fcpt_ctx *c, D **dst, const std::vector<T> &src) // D: T or const T
 {
     T *p = nullptr;
     if (int e = dev_alloc(c, &p, src.size()))

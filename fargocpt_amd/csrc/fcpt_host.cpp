@@ -204,8 +204,6 @@ void build_geometry(const fcpt_desc &d, const fcpt_split &s, const double *Radii
     for (auto *v : {&g.Rmed, &g.Rinf, &g.Rsup, &g.Surf, &g.InvRmed, &g.InvRinf, &g.InvSurf,
                     &g.InvDiffRmed, &g.InvDiffRsup, &g.InvDiffRsupRb})
         v->assign(n, 0.0);
-    const double invdphi = (double)d.nphi / (2.0 * M_PI);
-    (void)invdphi;
     for (int i = 0; i < n1; ++i) {
         const double ri = Radii[i + s.imin], rs = Radii[i + s.imin + 1];
         g.Rinf[i] = ri;

@@ -180,10 +180,11 @@ struct Dev {
     CArr Rmed, Rinf, Rsup, Surf, InvRmed, InvRinf, InvSurf, InvDiffRmed, InvDiffRsup, InvDiffRsupRb;
     const double *cosphi, *sinphi; // cos/sin(dphi * j), j < nphi (SideEuler.cpp:60-63)
     CArr cs_ring, nu_ring; // isothermal sound speed and alpha-viscosity per ring
-    // per-ring reciprocals used by the marching source kernel (host-evaluated, IEEE):
-    //   g_inv_dxt_src = 2/(dphi (Rsup+Rinf)), g_inv_rsum = 1/(Rsup+Rinf), g_inv_drmed2 = 1/(Rmed[i]^2-Rmed[i-1]^2),
-    //   g_inv_dra2 = 1/(Rinf[i+1]^2-Rinf[i]^2), g_inv_rmsum = 1/(Rmed[i]+Rmed[i-1])
+    // never filled and read by no kernel (null, as massflow is when unused; their values live in SrcRow): they only keep
+    // the members behind them where they are -- without them the compiler allocates the registers of several kernels
+    // differently (VGPRs, SGPR spills, the occupancy of two)
     CArr g_inv_dxt_src, g_inv_rsum, g_inv_drmed2, g_inv_dra2, g_inv_rmsum;
+    // per-ring factors (host-evaluated, IEEE):
     //   g_dxtheta = dphi Rmed, g_inv_dxtheta = 1/(dphi Rmed), g_dr_invsurf = (Rsup-Rinf) InvSurf, g_r_omega = Rmed OmegaFrame
     CArr g_dxtheta, g_inv_dxtheta, g_dr_invsurf, g_r_omega;
     CArr g_inv_omk;  // 1 / Omega_K(Rmed[i])
@@ -308,6 +309,34 @@ struct ParticleAdaptive {
     int max_attempts;                  // guard 9: accepted + rejected substeps per particle and call
     double rmin, rmax;                 // RMIN, RMAX of the descriptor: the drag kick is skipped outside (Rinf[0] < RMIN: ghost ring)
 };
+
+// ---- fcpt_tables.cpp: the host-only stages of fcpt_create (no HIP; fcpt_selftest_ring_tables runs them on any machine) ----
+
+// Everything fcpt_create uploads per ring (and per column: cosphi, sinphi), as host vectors.
+struct RingTables {
+    std::vector<double> cosphi, sinphi;     // nphi
+    std::vector<double> cs_ring, nu_ring;   // nr
+    std::vector<double> g_dxtheta, g_inv_dxtheta, g_dr_invsurf, g_r_omega, g_inv_omk, g_omk; // nr + 1, entry nr is 0
+    std::vector<double> g_ra3;              // nr + 2, entry nr + 1 is 0
+    std::vector<RadRow> rad;                // nr + 2
+    std::vector<ThetaRow> theta;            // nr
+    std::vector<SrcRow> src;                // nr + 8
+    DampRange damp[4][2];                   // [vrad, vaz, sigma, energy][inner, outer]
+    std::vector<double> fs, ts, fv, tv;     // nr + 1: Dev::dfac_s, dtau_s, dfac_v, dtau_v
+    std::vector<int> dtype[4];              // nr + 1: Dev::dtype_vr, dtype_va, dtype_sig, dtype_e
+    std::vector<DampRow> damp_rows;         // nr + 1
+    std::vector<int> ring_ref_damped;       // nr: 1 where a folded damping loads reference values
+    bool damp_any = false;                  // this slab holds rings of a damping zone
+    bool damp_foldable = false;             // ... and its damping can be folded into the transport (no "mean" target, Euler)
+};
+
+// what fcpt_create refuses before it looks for a device
+int validate_create(const fcpt_desc *d, const double *radii);
+double omega_kepler(const fcpt_desc &d, double r); // sqrt(G M / r^3)
+DampRange damp_range(const fcpt_desc &d, const fcpt_split &s, const HostGeometry &g, int is_vector, int type, int outer);
+void build_ring_tables(const fcpt_desc &d, const fcpt_split &s, const HostGeometry &g, RingTables &t);
+// the descriptor's and the split's scalars, and the default body (the central star at the origin)
+void fill_parameters(const fcpt_desc &d, const fcpt_split &s, const HostGeometry &g, Dev &P);
 
 } // namespace fcpt
 

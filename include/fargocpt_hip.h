@@ -775,6 +775,24 @@ int fcpt_profile_stop(fcpt_ctx *ctx, double *ms_total, int64_t *launches);
 int fcpt_selftest_chunk_tables(int32_t nr, int32_t nphi, int32_t n_cu, int32_t adiabatic, int32_t damp_inner, int32_t damp_outer,
                                int32_t *transport_tile_first_last, int32_t transport_capacity, int32_t *n_transport,
                                int32_t *source_seg_first_last, int32_t source_capacity, int32_t *n_source);
+/* Test hook, needs no GPU: one of the per-ring tables fcpt_create would upload for this descriptor and these global radii
+ * (the slab of d->rank), as rows x cols doubles in row-major order.  Integer columns are converted; the columns of a
+ * row table are the members of its row structure in declaration order (csrc/fcpt_internal.h).  `out` holds `capacity`
+ * doubles (0 with out = NULL: only rows and cols are returned), nr = the slab's rings:
+ *   FCPT_TABLE_SRC    nr + 8 rows, row m + 2 = iteration m of the marching source kernel (SrcRow, 40 columns)
+ *   FCPT_TABLE_RAD    nr + 2 rows, row k + 1 = radial interface k (RadRow, 4 columns)
+ *   FCPT_TABLE_THETA  nr rows (ThetaRow, 8 columns)
+ *   FCPT_TABLE_DAMP   nr + 1 rows (DampRow, 10 columns: fs, ts, fv, tv, tvr, tva, tsg, ten, pad[0], pad[1])
+ *   FCPT_TABLE_RING   nr + 2 rows, the plain per-ring arrays, each zero beyond its own length: cs_ring, nu_ring (nr);
+ *                     g_dxtheta, g_inv_dxtheta, g_dr_invsurf, g_r_omega, g_inv_omk, g_omk (nr + 1, entry nr is 0);
+ *                     g_ra3 (nr + 2); dfac_s, dtau_s, dfac_v, dtau_v, dtype_vr, dtype_va, dtype_sig, dtype_e (nr + 1);
+ *                     ring_ref_damped (nr) -- 18 columns in this order
+ *   FCPT_TABLE_DAMP_RANGES  9 rows of 6: row 2 q + o = (lo, hi, type, rlim, redge, tau) of field q (v_r, v_phi, Sigma, e)
+ *                     at the inner (o = 0) or outer edge; row 8 = (damp_any, damp_foldable, 0, 0, 0, 0)
+ *   FCPT_TABLE_AZIMUTH  nphi rows: cos(dphi j), sin(dphi j) */
+enum { FCPT_TABLE_SRC = 0, FCPT_TABLE_RAD, FCPT_TABLE_THETA, FCPT_TABLE_DAMP, FCPT_TABLE_RING, FCPT_TABLE_DAMP_RANGES, FCPT_TABLE_AZIMUTH };
+int fcpt_selftest_ring_tables(const fcpt_desc *d, const double *radii, int32_t table, double *out, int64_t capacity,
+                              int32_t *rows, int32_t *cols);
 /* Test hook: out[k] = 0.5 * flux_limiter(a[k], b[k]) (src/TransportEuler.cpp:306-337; limiter = FCPT_LIMITER_*) exactly
  * as the transport kernels evaluate it on the device -- the van Leer form there is branch-free (max(ab, 0) times a
  * guarded reciprocal of a + b) and its edge cases (+-0, denormal and cancelling sums) are what this call lets a test

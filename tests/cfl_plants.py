@@ -61,17 +61,25 @@ def case_desc(lib, nr, nphi, ideal=False, leapfrog=False, av="TW", fast=True, st
     return d
 
 
-def geometry(lib, d, radii):
-    """The slab's rings as init.cpp:169-225 forms them, and its active range (split.cpp:34-88)."""
+def geometry(lib, d, radii, pad=0):
+    """The slab's rings as init.cpp:169-225 forms them, and its active range (split.cpp:34-88).  `pad`: that many
+    rings beyond the slab's nr in every array (the reference keeps GEOM_PAD of them)."""
     s = lib.split_domain(d)
     nr = s.nr
-    ri = np.asarray(radii[s.imin:s.imin + nr], dtype=np.float64)
-    rs = np.asarray(radii[s.imin + 1:s.imin + nr + 1], dtype=np.float64)
+    ri = np.asarray(radii[s.imin:s.imin + nr + pad], dtype=np.float64)
+    rs = np.asarray(radii[s.imin + 1:s.imin + nr + pad + 1], dtype=np.float64)
     rmed = (2.0 / 3.0 * (rs * rs * rs - ri * ri * ri)) / (rs * rs - ri * ri)
     g = SimpleNamespace(nr=nr, nphi=d.nphi, imin=s.imin, first_active=s.radial_first_active,
                         active_size=s.radial_active_size, Rinf=ri, Rsup=rs, Rmed=rmed, InvRmed=1.0 / rmed,
                         InvDiffRsup=1.0 / (rs - ri), dphi=2.0 * math.pi / float(d.nphi),
                         invdphi=float(d.nphi) / (2.0 * math.pi))
+    g.is_first, g.is_last = bool(s.is_first), bool(s.is_last)
+    g.Surf = math.pi * (rs * rs - ri * ri) / float(d.nphi)
+    g.InvSurf = 1.0 / g.Surf
+    g.InvRinf = 1.0 / ri
+    g.InvDiffRsupRb = 1.0 / ((rs - ri) * rmed)
+    g.InvDiffRmed = np.zeros_like(rmed)   # rows 1 .. nr (init.cpp:219-221), 0 elsewhere
+    g.InvDiffRmed[1:nr + 1] = (1.0 / (rmed[1:] - rmed[:-1]))[:nr]
     g.dxr = rs - ri
     g.dxa = rmed * g.dphi
     g.cell = np.minimum(g.dxr, g.dxa)
