@@ -120,6 +120,12 @@ class ParticleIntegrator(C.Structure):
     _fields_ = [("kind", _i32), ("cartesian", _i32), ("max_attempts", _i32), ("_pad0", _i32)]
 
 
+class ParticleSlabs(C.Structure):
+    """fcpt_particle_slabs: particles on one of several slabs, the records per side and call, and the running totals."""
+    _fields_ = [("on", _i32), ("migrate_capacity", _i32), ("sent_inner", _u64), ("sent_outer", _u64), ("received", _u64),
+                ("deferred", _u64)]
+
+
 INTEGRATOR_MIDPOINT, INTEGRATOR_EXPLICIT = 0, 1
 PARTICLE_FIELDS = ("r", "phi", "r_dot", "phi_dot", "radius", "stokes")
 ADAPTIVE_FIELDS = ("timestep", "facold", "r_ddot", "phi_ddot")
@@ -193,6 +199,12 @@ class Library:
         p = ParticleParams()
         self.check(self.fn("particle_params_default")(C.byref(d), C.byref(p)), "particle_params_default")
         return p
+
+    def particles_slab_window(self, d: Desc, radii: np.ndarray):
+        """(r_lo, r_hi): the radii between which slab d.rank owns a particle; -inf / +inf at the grid's own edges.  No GPU."""
+        w = (_f64 * 2)()
+        self.check(self.fn("particles_slab_window")(C.byref(d), _as_dp(radii), w), "particles_slab_window")
+        return w[0], w[1]
 
     def philox4x32(self, counter, key) -> np.ndarray:
         """Ten rounds of Philox4x32 on the host: counter (4 words), key (2 words) -> 4 words."""
@@ -580,6 +592,33 @@ class Context:
         v = _i32()
         self._call("particles_follow_run_steps_get", C.byref(v))
         return bool(v.value)
+
+    # particles on several slabs: every slab holds all slots and steps the particles it owns
+    def particles_slabs(self, on: bool = True, migrate_capacity: int = 0):
+        """Opt in before particles_set on a context that is one of several slabs; migrate_capacity 0: what a message holds."""
+        p = ParticleSlabs(int(bool(on)), int(migrate_capacity), 0, 0, 0, 0)
+        self._call("particles_slabs", C.byref(p))
+
+    def particles_slabs_get(self) -> ParticleSlabs:
+        p = ParticleSlabs()
+        self._call("particles_slabs_get", C.byref(p))
+        return p
+
+    def particles_migrate_count(self) -> int:
+        n = _u64()
+        self._call("particles_migrate_count", C.byref(n))
+        return n.value
+
+    def particles_migrate_pack(self, send_inner, send_outer):
+        """Leavers into the two messages (numpy arrays of particles_migrate_count() doubles, device addresses, or None)."""
+        self._call("particles_migrate_pack", self._buf(send_inner), self._buf(send_outer))
+
+    def particles_migrate_unpack(self, recv_inner, recv_outer):
+        self._call("particles_migrate_unpack", self._buf(recv_inner), self._buf(recv_outer))
+
+    def particles_migrate(self):
+        """The collective over the context's communicator: pack, neighbour exchange, unpack."""
+        self._call("particles_migrate")
 
     def particles_normals(self, step: int) -> np.ndarray:
         """The deviates the live particles draw at counter `step` (particles_get's order); nothing is stepped."""

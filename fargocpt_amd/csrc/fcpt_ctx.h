@@ -129,6 +129,14 @@ struct fcpt_ctx {
     // iteration; part_step_offset: the device word behind ParticleArgs::step_offset, made when first switched on
     bool part_follow = false;
     unsigned long long *part_step_offset = nullptr;
+    // fcpt_particles_slabs (outlives fcpt_particles_set): the setting (its four totals live on the device: part_mtot), the
+    // ownership window, and -- made when first switched on -- the messages [send inner, send outer, recv inner, recv
+    // outer] of fcpt_exchange_count doubles each and the two per-call counters of k_particles_emigrate
+    fcpt_particle_slabs part_slabs = {0, 0, 0, 0, 0, 0};
+    double part_window[2] = {0.0, 0.0};
+    double *part_mbuf[4] = {};
+    unsigned int *part_mcnt = nullptr;
+    unsigned long long *part_mtot = nullptr;
     // fcpt_run_steps on launch-bound grids: a captured hipGraph of `graph_cycle` consecutive steps (the out-of-place
     // transport swaps grid pointers, so the launch arguments repeat with period 2), replayed while the host-side state
     // that decided the launches (the whole Dev view, the lazy-evaluation flags) is what it was at capture

@@ -425,6 +425,21 @@ double fcpt_particles_std_normal(uint64_t seed, uint64_t id, uint64_t step)
     return fcpt::particle_std_normal(seed, id, step);
 }
 
+// local_r_min / local_r_max of particles.cpp:527-529: Rinf of the first and one past the last row the slab owns
+int fcpt_particles_slab_window(const fcpt_desc *d, const double *radii, double window[2])
+{
+    if (!d || !radii || !window) {
+        fcpt::set_error("fcpt_particles_slab_window: null argument");
+        return FCPT_EINVAL;
+    }
+    fcpt_split s;
+    if (int rc = fcpt_split_domain(d, &s))
+        return rc;
+    window[0] = s.is_first ? -HUGE_VAL : radii[s.imin + FCPT_OVERLAP];
+    window[1] = s.is_last ? HUGE_VAL : radii[s.imin + s.nr - FCPT_OVERLAP];
+    return FCPT_OK;
+}
+
 int fcpt_split_domain(const fcpt_desc *d, fcpt_split *out)
 {
     if (!d || !out) {

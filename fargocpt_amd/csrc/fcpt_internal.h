@@ -299,6 +299,22 @@ struct ParticleArgs {
     // above): the step length is Dev::clk->dt, frame_angle the rounded product omega_frame * dt and the Philox counter
     // *step_offset + clk->n_hydro_iter (wrapping), so a replayed hipGraph needs no new arguments
     const unsigned long long *step_offset;
+    // fcpt_particles_slabs: the global index of the slab's row 0 (read by the slab kernels only; 0 otherwise)
+    int row0;
+};
+
+// fcpt_particles_slabs: what k_particles_emigrate / k_particles_immigrate need besides the arrays (kernels/particles.h)
+#define PARTICLE_RECORD_MIN 6  // slot, r, phi, r_dot, phi_dot, stokes
+#define PARTICLE_RECORD_MAX 10 // ... timestep, facold, r_ddot, phi_ddot
+struct ParticleMigrate {
+    double lo_sq, hi_sq;      // squared edges of the ownership window (-inf / +inf without a neighbour on that side)
+    int has_inner, has_outer; // this edge has a neighbour
+    int cartesian;            // d^2 = x^2 + y^2 instead of r^2
+    int capacity;             // records per side and call
+    int rec;                  // doubles per record: PARTICLE_RECORD_MIN, or _MAX with the adaptive arrays
+    double *inner, *outer;    // the two messages (null: that side is skipped)
+    unsigned int *cnt;        // [2]: particles selected for the inner / outer side in this call (zero between calls)
+    unsigned long long *tot;  // [4]: sent_inner, sent_outer, received, deferred since fcpt_create
 };
 
 // the per-particle state of the explicit adaptive integrator (k_particles_step_explicit): a second device block,

@@ -87,8 +87,11 @@ struct DiskBodies {
 };
 size_t disk_on_bodies_blocks(const Dev &P); // blocks of the first stage: `part` holds 4 * n * blocks doubles, `out` 4 * n
 void launch_disk_on_bodies(const Dev &P, int n, const DiskBodies &B, double *part, double *out, hipStream_t st);
-void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st);
-void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const ParticleAdaptive &X, bool cartesian, hipStream_t st);
+void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st, bool slab = false);
+void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const ParticleAdaptive &X, bool cartesian, hipStream_t st,
+                               bool slab = false);
+void launch_particles_emigrate(const ParticleArgs &A, const ParticleAdaptive &X, const ParticleMigrate &M, hipStream_t st);
+void launch_particles_immigrate(const ParticleArgs &A, const ParticleAdaptive &X, const ParticleMigrate &M, hipStream_t st);
 void launch_particles_timestep_init(const Dev &P, const ParticleArgs &A, const ParticleAdaptive &X, bool cartesian, hipStream_t st);
 void launch_particles_normals(int n, const unsigned long long *id, unsigned long long seed, unsigned long long step, double *snv,
                               hipStream_t st);

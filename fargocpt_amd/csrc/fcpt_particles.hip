@@ -1,7 +1,9 @@
 // Dust particles of the C ABI: device state, the launch of k_particles_step (kernels/particles.h), the switches of
 // drag and diffusion and the blocking reads.  Replaces particles::integrate with ParticleIntegrator: midpoint (particles/particles.cpp:1525-1557,1579-1672)
 // and ParticleIntegrator: explicit (:1677-2014, k_particles_step_explicit)
-// for one radial slab; see include/fargocpt_hip.h for what is and is not covered.
+// for one radial slab, and -- fcpt_particles_slabs -- for a slab among several: ownership by window, and particles::move()'s
+// hand-over to the radial neighbours (:2016-2161) as records in messages of the ghost rings' length; see
+// include/fargocpt_hip.h for what is and is not covered.
 #include "fcpt_ctx.h"
 
 #include <algorithm>
@@ -55,7 +57,16 @@ int particles_wait(fcpt_ctx *c, const char *who)
     unsigned long long id = 0;
     if (slot < (size_t)c->part.n)
         HIPCHK(hipMemcpy(&id, c->part_id + slot, sizeof(id), hipMemcpyDeviceToHost));
-    if (guard >= 9 && guard <= 10)
+    if (guard == 12)
+        set_error("%s: guard 12: a migration message held a record count beyond the capacity or a slot index outside 0 .. %d; "
+                  "nothing of it was written",
+                  who, c->part.n - 1);
+    else if (guard == 11)
+        set_error("%s: particle id %llu tripped guard 11 (the step needs a gas row beyond the rings of slab %d on a side that "
+                  "has a neighbour: it moved more than the overlap in one step, or its migration was deferred too long) and was "
+                  "left unchanged",
+                  who, id, c->d.rank);
+    else if (guard >= 9 && guard <= 10)
         set_error("%s: particle id %llu tripped guard %d (%s) and was left unchanged", who, id, guard, kGuardNames[guard]);
     else
         set_error("%s: particle id %llu tripped guard %d of calc_tstop (%s) and was left unchanged", who, id, guard,
@@ -109,6 +120,119 @@ bool ids_distinct(const unsigned long long *id, size_t n)
     return std::adjacent_find(v.begin(), v.end()) == v.end();
 }
 
+// ---- fcpt_particles_slabs -------------------------------------------------------------------------------------------
+// the context takes particles as one of several slabs: the slab kernels, ownership and migration apply
+bool on_slab(const fcpt_ctx *c)
+{
+    return c->part_slabs.on != 0 && c->d.nranks > 1;
+}
+size_t message_doubles(const fcpt_ctx *c)
+{
+    uint64_t cnt = 0;
+    (void)fcpt_exchange_count(c, &cnt);
+    return (size_t)cnt;
+}
+int record_doubles(const fcpt_ctx *c)
+{
+    return c->part_adapt_block ? PARTICLE_RECORD_MAX : PARTICLE_RECORD_MIN;
+}
+// records per side and call: the caller's, or what a message holds, whichever is smaller
+int migrate_capacity(const fcpt_ctx *c)
+{
+    const int fit = (int)((message_doubles(c) - 1) / (size_t)record_doubles(c));
+    const int asked = c->part_slabs.migrate_capacity;
+    return asked > 0 && asked < fit ? asked : fit;
+}
+// squared edges of the ownership window; a side without a neighbour has none
+void window_sq(const fcpt_ctx *c, double *lo_sq, double *hi_sq)
+{
+    *lo_sq = c->s.is_first ? -HUGE_VAL : c->part_window[0] * c->part_window[0];
+    *hi_sq = c->s.is_last ? HUGE_VAL : c->part_window[1] * c->part_window[1];
+}
+void migrate_args(const fcpt_ctx *c, double *inner, double *outer, ParticleMigrate *M)
+{
+    window_sq(c, &M->lo_sq, &M->hi_sq);
+    M->has_inner = !c->s.is_first;
+    M->has_outer = !c->s.is_last;
+    M->cartesian = c->part_integ.kind == 1 && c->part_integ.cartesian != 0;
+    M->capacity = migrate_capacity(c);
+    M->rec = record_doubles(c);
+    M->inner = M->has_inner ? inner : nullptr;
+    M->outer = M->has_outer ? outer : nullptr;
+    M->cnt = c->part_mcnt;
+    M->tot = c->part_mtot;
+}
+bool buffer_on_device(const void *p)
+{
+    if (!p)
+        return true;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError(); // plain host memory: not an error here
+        return false;
+    }
+    return a.type == hipMemoryTypeDevice;
+}
+int migrate_check(const fcpt_ctx *c, const char *who)
+{
+    if (!c) {
+        set_error("%s: null context", who);
+        return FCPT_EINVAL;
+    }
+    if (!on_slab(c)) {
+        set_error("%s needs fcpt_particles_slabs with on = 1 on a context that is one of several slabs", who);
+        return FCPT_EINVAL;
+    }
+    return FCPT_OK;
+}
+// k_particles_emigrate into `inner` / `outer` (device, or host: through the context's own messages)
+int migrate_pack(fcpt_ctx *c, double *send_inner, double *send_outer)
+{
+    if (c->part.n <= 0) { // nobody to send: empty messages
+        const double zero = 0.0;
+        for (double *m : {send_inner, send_outer})
+            if (m)
+                HIPCHK(hipMemcpyAsync(m, &zero, sizeof(zero), hipMemcpyDefault, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream)); // `zero` leaves scope
+        return FCPT_OK;
+    }
+    join_side(c);
+    const bool dev_in = buffer_on_device(send_inner), dev_out = buffer_on_device(send_outer);
+    ParticleMigrate M;
+    migrate_args(c, !send_inner ? nullptr : (dev_in ? send_inner : c->part_mbuf[0]),
+                 !send_outer ? nullptr : (dev_out ? send_outer : c->part_mbuf[1]), &M);
+    launch_particles_emigrate(c->part, c->part_adapt, M, c->stream);
+    HIPCHK(hipGetLastError());
+    const size_t bytes = message_doubles(c) * sizeof(double);
+    if (M.inner && !dev_in)
+        HIPCHK(hipMemcpyAsync(send_inner, c->part_mbuf[0], bytes, hipMemcpyDeviceToHost, c->stream));
+    if (M.outer && !dev_out)
+        HIPCHK(hipMemcpyAsync(send_outer, c->part_mbuf[1], bytes, hipMemcpyDeviceToHost, c->stream));
+    if ((M.inner && !dev_in) || (M.outer && !dev_out))
+        HIPCHK(hipStreamSynchronize(c->stream)); // the host buffers are complete when the call returns
+    return FCPT_OK;
+}
+int migrate_unpack(fcpt_ctx *c, const double *recv_inner, const double *recv_outer)
+{
+    if (c->part.n <= 0)
+        return FCPT_OK;
+    join_side(c);
+    const bool dev_in = buffer_on_device(recv_inner), dev_out = buffer_on_device(recv_outer);
+    const size_t bytes = message_doubles(c) * sizeof(double);
+    if (recv_inner && !dev_in)
+        HIPCHK(hipMemcpyAsync(c->part_mbuf[2], recv_inner, bytes, hipMemcpyHostToDevice, c->stream));
+    if (recv_outer && !dev_out)
+        HIPCHK(hipMemcpyAsync(c->part_mbuf[3], recv_outer, bytes, hipMemcpyHostToDevice, c->stream));
+    ParticleMigrate M;
+    migrate_args(c, !recv_inner ? nullptr : (dev_in ? const_cast<double *>(recv_inner) : c->part_mbuf[2]),
+                 !recv_outer ? nullptr : (dev_out ? const_cast<double *>(recv_outer) : c->part_mbuf[3]), &M);
+    launch_particles_immigrate(c->part, c->part_adapt, M, c->stream);
+    HIPCHK(hipGetLastError());
+    if ((recv_inner && !dev_in) || (recv_outer && !dev_out))
+        HIPCHK(hipStreamSynchronize(c->stream)); // the caller's host buffers are free again
+    return FCPT_OK;
+}
+
 } // namespace
 
 namespace fcpt {
@@ -118,6 +242,12 @@ int particles_loop_check(const fcpt_ctx *c)
 {
     if (!c->part_follow)
         return FCPT_OK;
+    if (c->d.nranks > 1) {
+        set_error("fcpt_run_steps: fcpt_particles_follow_run_steps is on, and particles inside the multi-slab loop are not "
+                  "covered (this context is slab %d of %d): step them with fcpt_particles_step and fcpt_particles_migrate",
+                  c->d.rank, c->d.nranks);
+        return FCPT_EINVAL;
+    }
     if (c->d.integrator == FCPT_INTEGRATOR_LEAPFROG) {
         set_error("fcpt_run_steps: fcpt_particles_follow_run_steps is on, and the particle step has no place in Integrator: "
                   "Leapfrog (switch it off, or use Integrator: Euler)");
@@ -215,7 +345,7 @@ int fcpt_particles_set(fcpt_ctx *c, const fcpt_particle_params *prm, int64_t n, 
         set_error("fcpt_particles_set: null argument");
         return FCPT_EINVAL;
     }
-    if (n > 0 && c->d.nranks != 1) {
+    if (n > 0 && c->d.nranks != 1 && !c->part_slabs.on) {
         set_error("fcpt_particles_set: particles need the whole grid in one slab (this context is slab %d of %d)", c->d.rank,
                   c->d.nranks);
         return FCPT_EINVAL;
@@ -267,7 +397,21 @@ int fcpt_particles_set(fcpt_ctx *c, const fcpt_particle_params *prm, int64_t n, 
     chk(hipMemcpyAsync(c->part_id, id, nn * 8, hipMemcpyHostToDevice, c->stream));
     for (int k = 0; k < 6; ++k)
         chk(hipMemcpyAsync(arr + k * nn, src[k], nn * 8, hipMemcpyHostToDevice, c->stream));
-    chk(hipMemsetAsync(A.alive, 1, nn, c->stream));
+    std::vector<unsigned char> owned; // (outlives the copy)
+    if (on_slab(c)) {
+        // every slab is handed the full list and owns what starts inside its window: r_lo^2 <= d^2 < r_hi^2
+        double lo_sq, hi_sq;
+        window_sq(c, &lo_sq, &hi_sq);
+        const bool cart = c->part_integ.kind == 1 && c->part_integ.cartesian != 0;
+        owned.resize(nn);
+        for (size_t k = 0; k < nn; ++k) {
+            const double d2 = cart ? r[k] * r[k] + phi[k] * phi[k] : r[k] * r[k];
+            owned[k] = lo_sq <= d2 && d2 < hi_sq;
+        }
+        chk(hipMemcpyAsync(A.alive, owned.data(), nn, hipMemcpyHostToDevice, c->stream));
+    } else {
+        chk(hipMemsetAsync(A.alive, 1, nn, c->stream));
+    }
     chk(hipStreamSynchronize(c->stream));
     if (rc) {
         particles_free(c);
@@ -287,6 +431,7 @@ int fcpt_particles_set(fcpt_ctx *c, const fcpt_particle_params *prm, int64_t n, 
     A.cf_growth = c->geo.cf_growth;
     A.cf_inv_log_growth = c->geo.cf_inv_log_growth;
     A.cf_opt_const = c->geo.cf_opt_const;
+    A.row0 = on_slab(c) ? c->s.imin : 0;
     return FCPT_OK;
 }
 
@@ -322,9 +467,9 @@ int fcpt_particles_step(fcpt_ctx *c, double dt, double indirect_x, double indire
         X.max_attempts = c->part_integ.max_attempts > 0 ? c->part_integ.max_attempts : kDefaultMaxAttempts;
         X.rmin = c->d.rmin;
         X.rmax = c->d.rmax;
-        launch_particles_explicit(P, A, X, c->part_integ.cartesian != 0, c->stream);
+        launch_particles_explicit(P, A, X, c->part_integ.cartesian != 0, c->stream, on_slab(c));
     } else {
-        launch_particles(P, A, c->stream);
+        launch_particles(P, A, c->stream, on_slab(c));
     }
     HIPCHK(hipGetLastError());
     return FCPT_OK;
@@ -586,6 +731,109 @@ int fcpt_particles_normals(fcpt_ctx *c, uint64_t step, int64_t capacity, double 
         if (alive[s])
             snv[k++] = host[s];
     return FCPT_OK;
+}
+
+// ---- particles on several slabs: the setting, the messages, the collective -----------------------------------------------
+
+int fcpt_particles_slabs(fcpt_ctx *c, const fcpt_particle_slabs *p)
+{
+    if (!c || !p) {
+        set_error("fcpt_particles_slabs: null argument");
+        return FCPT_EINVAL;
+    }
+    if (p->on != 0 && p->on != 1) {
+        set_error("fcpt_particles_slabs: on = %d is neither 0 nor 1", (int)p->on);
+        return FCPT_EINVAL;
+    }
+    const int fit = (int)((message_doubles(c) - 1) / (size_t)PARTICLE_RECORD_MIN);
+    if (p->migrate_capacity < 0 || p->migrate_capacity > fit) {
+        set_error("fcpt_particles_slabs: migrate_capacity = %d outside 0 .. %d, what a message of %zu doubles holds (0 selects "
+                  "the built-in value)",
+                  (int)p->migrate_capacity, fit, message_doubles(c));
+        return FCPT_EINVAL;
+    }
+    if (c->part.n > 0 && (p->on != 0) != (c->part_slabs.on != 0) && c->d.nranks > 1) {
+        set_error("fcpt_particles_slabs: switch it before fcpt_particles_set (the context holds %d particle slots)", c->part.n);
+        return FCPT_EINVAL;
+    }
+    if (p->on && !c->part_mtot) {
+        if (int rc = fcpt_particles_slab_window(&c->d, c->radii.data(), c->part_window))
+            return rc;
+        for (int k = 0; k < 4; ++k)
+            if (int rc = dev_alloc(c, &c->part_mbuf[k], message_doubles(c)))
+                return rc;
+        if (int rc = dev_alloc(c, &c->part_mcnt, 2))
+            return rc;
+        if (int rc = dev_alloc(c, &c->part_mtot, 4))
+            return rc;
+    }
+    c->part_slabs.on = p->on;
+    c->part_slabs.migrate_capacity = p->migrate_capacity;
+    return FCPT_OK;
+}
+
+int fcpt_particles_slabs_get(fcpt_ctx *c, fcpt_particle_slabs *out)
+{
+    if (!c || !out)
+        return FCPT_EINVAL;
+    *out = c->part_slabs;
+    if (c->part_mtot) {
+        unsigned long long tot[4];
+        HIPCHK(hipMemcpyAsync(tot, c->part_mtot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        out->sent_inner = tot[0];
+        out->sent_outer = tot[1];
+        out->received = tot[2];
+        out->deferred = tot[3];
+    }
+    return FCPT_OK;
+}
+
+int fcpt_particles_migrate_count(fcpt_ctx *c, uint64_t *count)
+{
+    return fcpt_exchange_count(c, count);
+}
+
+int fcpt_particles_migrate_pack(fcpt_ctx *c, double *send_inner, double *send_outer)
+{
+    if (int rc = migrate_check(c, "fcpt_particles_migrate_pack"))
+        return rc;
+    ProfScope prof_scope(c);
+    return migrate_pack(c, send_inner, send_outer);
+}
+
+int fcpt_particles_migrate_unpack(fcpt_ctx *c, const double *recv_inner, const double *recv_outer)
+{
+    if (int rc = migrate_check(c, "fcpt_particles_migrate_unpack"))
+        return rc;
+    ProfScope prof_scope(c);
+    return migrate_unpack(c, recv_inner, recv_outer);
+}
+
+// pack, the neighbour exchange of the ghost rings' communicator with the messages in its place, unpack: one stream
+int fcpt_particles_migrate(fcpt_ctx *c)
+{
+    if (int rc = migrate_check(c, "fcpt_particles_migrate"))
+        return rc;
+    if (!c->comm) {
+        set_error("fcpt_particles_migrate needs fcpt_comm_init or fcpt_comm_init_host");
+        return FCPT_EINVAL;
+    }
+    ProfScope prof_scope(c);
+    double *s_in = c->peer_inner >= 0 ? c->part_mbuf[0] : nullptr, *s_out = c->peer_outer >= 0 ? c->part_mbuf[1] : nullptr;
+    double *r_in = c->peer_inner >= 0 ? c->part_mbuf[2] : nullptr, *r_out = c->peer_outer >= 0 ? c->part_mbuf[3] : nullptr;
+    if (c->part.n <= 0) { // the neighbours still wait for this slab's messages: empty ones
+        for (double *m : {s_in, s_out})
+            if (m)
+                HIPCHK(hipMemsetAsync(m, 0, sizeof(double), c->stream));
+    } else if (int rc = migrate_pack(c, s_in, s_out)) {
+        return rc;
+    }
+    const int rc = comm_neighbour_exchange(c->comm, c->peer_inner, s_in, r_in, c->peer_outer, s_out, r_out, message_doubles(c),
+                                           c->stream);
+    if (rc)
+        return rc == FCPT_EHIP ? FCPT_ECOMM : rc;
+    return migrate_unpack(c, r_in, r_out);
 }
 
 } // extern "C"

@@ -534,11 +534,22 @@ void launch_disk_on_bodies(const Dev &P, int n, const DiskBodies &B, double *par
 }
 
 // one lane per particle slot (dead slots return at once); the view's state grids are those of the start of the step
-void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st)
+// slab: the context is one of several slabs (fcpt_particles_slabs; host-argument form only: fcpt_run_steps refuses it)
+void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st, bool slab)
 {
     if (A.n <= 0)
         return;
     const dim3 grid((A.n + 255) / 256), block(256);
+    if (slab) {
+        with_bool(P.adiabatic, [&](auto ADI) {
+            with_bool(A.gas_drag != 0, [&](auto DRAG) {
+                with_bool(A.diffusion != 0, [&](auto DIFF) {
+                    KLAUNCH(KID_PARTICLES, (k_particles_step<TARG(ADI), TARG(DRAG), TARG(DIFF), false, true>), grid, block, P, A);
+                });
+            });
+        });
+        return;
+    }
     with_bool(P.adiabatic, [&](auto ADI) {
         with_bool(A.gas_drag != 0, [&](auto DRAG) {
             with_bool(A.diffusion != 0, [&](auto DIFF) {
@@ -551,7 +562,8 @@ void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st)
 }
 
 // ParticleIntegrator: explicit -- one lane per particle slot, one launch; the block size stands beside the kernel
-void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const ParticleAdaptive &X, bool cartesian, hipStream_t st)
+void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const ParticleAdaptive &X, bool cartesian, hipStream_t st,
+                               bool slab)
 {
     if (A.n <= 0)
         return;
@@ -559,7 +571,10 @@ void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const Partic
     with_bool(P.adiabatic, [&](auto ADI) {
         with_bool(A.gas_drag != 0, [&](auto DRAG) {
             with_bool(cartesian, [&](auto CART) {
-                if (A.step_offset)
+                if (slab)
+                    KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit_slab<TARG(ADI), TARG(DRAG), TARG(CART)>), grid, block, P,
+                            A, X);
+                else if (A.step_offset)
                     KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit_clock<TARG(ADI), TARG(DRAG), TARG(CART)>), grid, block, P,
                             A, X);
                 else
@@ -587,6 +602,21 @@ void launch_particles_normals(int n, const unsigned long long *id, unsigned long
 void launch_particles_counter_offset(unsigned long long *offset, unsigned long long counter, const DevClock *clk, hipStream_t st)
 {
     hipLaunchKernelGGL(k_particles_counter_offset, dim3(1), dim3(1), 0, st, offset, counter, clk);
+}
+
+// fcpt_particles_slabs: one lane per slot, then one lane for the counts; the receiver's grid covers the capacity of a side
+void launch_particles_emigrate(const ParticleArgs &A, const ParticleAdaptive &X, const ParticleMigrate &M, hipStream_t st)
+{
+    if (A.n <= 0)
+        return;
+    hipLaunchKernelGGL(k_particles_emigrate, dim3((A.n + 255) / 256), dim3(256), 0, st, A, X, M);
+    hipLaunchKernelGGL(k_particles_emigrate_finish, dim3(1), dim3(1), 0, st, M);
+}
+void launch_particles_immigrate(const ParticleArgs &A, const ParticleAdaptive &X, const ParticleMigrate &M, hipStream_t st)
+{
+    if (A.n <= 0 || M.capacity <= 0)
+        return;
+    hipLaunchKernelGGL(k_particles_immigrate, dim3((M.capacity + 255) / 256, 2), dim3(256), 0, st, A, X, M);
 }
 
 // rings whose CFL terms read nothing the ghost exchange or the boundary kernels write: ring i reads rows i

@@ -41,6 +41,9 @@ __device__ __forceinline__ double particle_check_angle(double phi)
 // Largest i in [0, nr-1] with Rinf[i] <= r (get_rinf_id with the release build's clamp).  The closed form of the
 // spacing gives the guess; where it is off (rounding at an interface, a radii array of the caller's own) a binary
 // search over the context's array decides, so the result is right for any monotonic grid.
+// SLAB: the context is one of several slabs (fcpt_particles_slabs).  cf_rmin is the global Rmin, so the closed form counts
+// global rows: the slab's first row, A.row0, comes off the guess, in integers, before it is checked against the local Rinf.
+template <bool SLAB = false>
 __device__ __forceinline__ int particle_rinf_id(const double *Rinf, int nr, const ParticleArgs &A, double r)
 {
     double did;
@@ -50,7 +53,11 @@ __device__ __forceinline__ int particle_rinf_id(const double *Rinf, int nr, cons
         did = (r - A.cf_rmin) * A.cf_growth;
     else
         did = log((r - A.cf_rmin) * A.cf_opt_const + 1.0) * A.cf_inv_log_growth;
-    int g = (int)floor(dmin(dmax(did, -1.0), (double)nr)) + 1;
+    int g;
+    if (SLAB)
+        g = (int)floor(dmin(dmax(did, -1.0), (double)(A.row0 + nr))) + 1 - A.row0;
+    else
+        g = (int)floor(dmin(dmax(did, -1.0), (double)nr)) + 1;
     g = g < 0 ? 0 : (g > nr - 1 ? nr - 1 : g);
     if (Rinf[g] <= r && (g == nr - 1 || r < Rinf[g + 1]))
         return g;
@@ -108,12 +115,12 @@ struct ParticleGasAt {
     double rho, temperature, vg_radial, vg_azimuthal;
     int ib_raw, ja;
 };
-template <bool ADI>
+template <bool ADI, bool SLAB = false>
 __device__ __forceinline__ ParticleGasAt particle_interpolate(const Dev &P, const ParticleArgs &A, double r_tmp, double phi1)
 {
     const int nr = P.nr, nphi = P.nphi;
     const double *Rinf = P.Rinf.p, *Rmed = P.Rmed.p;
-    const int ia = particle_rinf_id(Rinf, nr, A, r_tmp);
+    const int ia = particle_rinf_id<SLAB>(Rinf, nr, A, r_tmp);
     const int ib_raw = r_tmp >= Rmed[ia] ? ia : ia - 1; // Rinf[ia] < Rmed[ia] < Rinf[ia+1]
     const int ib = ib_raw < 0 ? 0 : (ib_raw > nr - 2 ? nr - 2 : ib_raw);
     // (phi1 is in [0, 2 pi]: where the product rounds up to nphi the particle still belongs to the last column)
@@ -220,6 +227,24 @@ template <bool ADI> __device__ __forceinline__ double particle_gas_diffusion(con
     return P.alpha * cs * (cs * P.g_inv_omk.p[i]);
 }
 
+// Guard 11 (SLAB only; integer tests, no floating expression of the step is touched): the step needs a gas row beyond the
+// slab's rings on a side that has a neighbour, where a one-slab run reads real gas and the clamps above would extrapolate.
+// `row` is the lower row of a cell-centred interpolation (rows row, row + 1, and up to row + 2 of v_r, whose row nr the
+// ghost exchange does not refresh: lo = 0, hi = nr - 3) or the row of the diffusion kick (rows row - 1 .. row + 1, and the
+// one-slab rule that leaves d rho / dr zero in rows 0 and Nr - 1 of the GLOBAL grid: lo = 1, hi = nr - 2).  A position
+// outside [Rinf[0], Rinf[nr]) of the slab ends at row -1 or nr - 1 by the clamps and trips as well.
+#define PARTICLE_GUARD_OFF_SLAB 11
+#define PARTICLE_GUARD_MESSAGE 12
+// the guard number of a branch that exists on one slab as well: guard 11 comes first
+template <bool SLAB> __device__ __forceinline__ int particle_guard(bool off_slab, int guard)
+{
+    return SLAB && off_slab ? PARTICLE_GUARD_OFF_SLAB : guard;
+}
+template <bool SLAB> __device__ __forceinline__ bool particle_off_slab(const Dev &P, int row, int lo, int hi)
+{
+    return SLAB && ((!P.is_first && row < lo) || (!P.is_last && row > hi));
+}
+
 // The three per-step scalars of a launch.  fcpt_particles_step passes them by value (A.step_offset is null); queued by
 // fcpt_run_steps they come from the device clock, because a replayed hipGraph repeats its arguments: the step length in
 // force, OmegaFrame * dt as ONE rounded product -- what the host-stepped loop passes; written inline the product could be
@@ -257,7 +282,8 @@ template <bool DEV> __device__ __forceinline__ unsigned long long particle_count
 // a second interpolation, at the end position, and calc_tstop with the velocities of the end of the step.
 // DEPARTURE from the reference: rho, d rho / dr and D_g of the kick come from the current Sigma (and e); the reference
 // evaluates them at init and refreshes them only under Disk: yes, from a RHO it refreshes only with the drag on.
-template <bool ADI, bool DRAG, bool DIFF, bool DEV>
+// SLAB: one of several slabs -- the cell search counts from the slab's first row and guard 11 is held; nothing else differs.
+template <bool ADI, bool DRAG, bool DIFF, bool DEV, bool SLAB = false>
 __global__ void __launch_bounds__(256) k_particles_step(const Dev P, const ParticleArgs A)
 {
     const int n = blockIdx.x * 256 + threadIdx.x;
@@ -284,25 +310,28 @@ __global__ void __launch_bounds__(256) k_particles_step(const Dev P, const Parti
     const double r_tmp = fmin(fmax(r1, Rinf[0]), Rinf[nr]); // Rsup[nr-1] = Rinf[nr]
     double tstop = 1e100, minus_r_dotel_r = 0.0, minus_l_rel = 0.0;
     int ib_raw, ja;
+    bool off_slab = false; // guard 11 (SLAB): joins the guards of calc_tstop where they branch, or waits for the stores
     if (DRAG) {
-        const ParticleGasAt g = particle_interpolate<ADI>(P, A, r_tmp, phi1);
+        const ParticleGasAt g = particle_interpolate<ADI, SLAB>(P, A, r_tmp, phi1);
         ib_raw = g.ib_raw;
         ja = g.ja;
+        off_slab = particle_off_slab<SLAB>(P, ib_raw, 0, nr - 3);
         // calculate_gas_drag_expmid
         minus_r_dotel_r = g.vg_radial - r_dot0;
         minus_l_rel = r1 * g.vg_azimuthal - l0;
         const double vrel_phi = g.vg_azimuthal - phi_dot0 * r0;
         const double vrel = sqrt(minus_r_dotel_r * minus_r_dotel_r + vrel_phi * vrel_phi);
         // the reference's die() guards: the particle stays as it was and is reported
-        if (const int guard = particle_calc_tstop(A, radius, g.rho, vrel, g.temperature, tstop)) {
+        if (const int guard = particle_guard<SLAB>(off_slab, particle_calc_tstop(A, radius, g.rho, vrel, g.temperature, tstop))) {
             *A.status = (unsigned long long)guard | ((unsigned long long)n << 8); // any one of the tripped particles
             return;
         }
     } else { // the cell of the smoothing length alone
-        const int ia = particle_rinf_id(Rinf, nr, A, r_tmp);
+        const int ia = particle_rinf_id<SLAB>(Rinf, nr, A, r_tmp);
         ib_raw = r_tmp >= Rmed[ia] ? ia : ia - 1;
         ja = (int)floor(phi1 * P.invdphi);
         ja = ja < 0 ? 0 : (ja > nphi - 1 ? nphi - 1 : ja);
+        off_slab = particle_off_slab<SLAB>(P, ib_raw, 0, nr - 3);
     }
 
     // ---- calculate_dust_smoothing: H of cell (rmed_id(r1), inf_azimuthal_id(phi1)) ------------------------------
@@ -353,6 +382,10 @@ __global__ void __launch_bounds__(256) k_particles_step(const Dev P, const Parti
     const double r3 = r1 + r_dot2 * hfdt;
     double phi3 = particle_check_angle(phi1 + 0.5 * (l2 / (r1 * r1) + l2 / (r3 * r3)) * hfdt);
     if (!DIFF) {
+        if (SLAB && !DRAG && off_slab) {
+            *A.status = (unsigned long long)PARTICLE_GUARD_OFF_SLAB | ((unsigned long long)n << 8);
+            return;
+        }
         // move(): escaped particles leave; rotate(): the frame's turn over the step
         const double r3sq = r3 * r3;
         if (r3sq > A.escape_max_sq || r3sq < A.escape_min_sq)
@@ -368,10 +401,12 @@ __global__ void __launch_bounds__(256) k_particles_step(const Dev P, const Parti
     const double phi_dot3 = l2 / (r3 * r3);
     const double omega_k3 = sqrt(P.G * P.Mc / (r3 * r3 * r3));
     if (!DRAG) { // check_tstop at the end position
-        const ParticleGasAt g = particle_interpolate<ADI>(P, A, fmin(fmax(r3, Rinf[0]), Rinf[nr]), phi3);
+        const ParticleGasAt g = particle_interpolate<ADI, SLAB>(P, A, fmin(fmax(r3, Rinf[0]), Rinf[nr]), phi3);
+        off_slab = off_slab || particle_off_slab<SLAB>(P, g.ib_raw, 0, nr - 3);
         const double dv_r = g.vg_radial - r_dot2;
         const double dv_phi = g.vg_azimuthal - phi_dot3 * r3;
-        if (const int guard = particle_calc_tstop(A, radius, g.rho, sqrt(dv_r * dv_r + dv_phi * dv_phi), g.temperature, tstop)) {
+        if (const int guard = particle_guard<SLAB>(
+                off_slab, particle_calc_tstop(A, radius, g.rho, sqrt(dv_r * dv_r + dv_phi * dv_phi), g.temperature, tstop))) {
             *A.status = (unsigned long long)guard | ((unsigned long long)n << 8);
             return;
         }
@@ -380,7 +415,8 @@ __global__ void __launch_bounds__(256) k_particles_step(const Dev P, const Parti
     // ---- diffuse_dust / kick_length: values of the particle's cell, no interpolation -------------------------------
     const double St2 = stokes * stokes;
     const double Sc = (1.0 + St2) * (1.0 + St2) / (1.0 + 4.0 * St2); // Youdin & Lithwick 2007, eq. 37
-    const int ik = particle_rinf_id(Rinf, nr, A, r3);
+    const int ik = particle_rinf_id<SLAB>(Rinf, nr, A, r3);
+    const bool off_kick = particle_off_slab<SLAB>(P, ik, 1, nr - 2);
     int jk = (int)floor(phi3 * P.invdphi);
     jk = jk < 0 ? 0 : (jk > nphi - 1 ? nphi - 1 : jk);
     const double Dd = particle_gas_diffusion<ADI>(P, ik, jk) / Sc;
@@ -395,6 +431,10 @@ __global__ void __launch_bounds__(256) k_particles_step(const Dev P, const Parti
     const double q = sigma * snv / r3;
     const double corr_2d = r3 * (sqrt(1.0 + q * q) - 1.0); // the missing diffusion tangential to r
     const double r4 = r3 + (mean + snv * sigma + corr_2d);
+    if (SLAB && off_kick) { // (ahead of the first store)
+        *A.status = (unsigned long long)PARTICLE_GUARD_OFF_SLAB | ((unsigned long long)n << 8);
+        return;
+    }
     // move() on the kicked radius (r4 <= 0 has left as well); rotate()
     const double r4sq = r4 * r4;
     if (r4sq > A.escape_max_sq || r4sq < A.escape_min_sq || !(r4 > 0.0))
@@ -486,6 +526,7 @@ __device__ __forceinline__ void particle_accel(const Dev &P, const ParticleArgs 
 
 #define PARTICLES_KERNEL k_particles_step_explicit
 #define PARTICLES_DEV false
+#define PARTICLES_SLAB false
 #include "particles_explicit_kernel.h"
 #undef PARTICLES_KERNEL
 #undef PARTICLES_DEV
@@ -494,6 +535,15 @@ __device__ __forceinline__ void particle_accel(const Dev &P, const ParticleArgs 
 #include "particles_explicit_kernel.h"
 #undef PARTICLES_KERNEL
 #undef PARTICLES_DEV
+#undef PARTICLES_SLAB
+// one of several slabs (fcpt_particles_slabs): the host-argument form with the slab's cell search and guard 11
+#define PARTICLES_KERNEL k_particles_step_explicit_slab
+#define PARTICLES_DEV false
+#define PARTICLES_SLAB true
+#include "particles_explicit_kernel.h"
+#undef PARTICLES_KERNEL
+#undef PARTICLES_DEV
+#undef PARTICLES_SLAB
 
 // init_particle_timestep (:248-374): Hairer's starting step with rsmooth = 0.05, facold = 1e-4
 template <bool CART> __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
@@ -552,4 +602,121 @@ template <bool CART> __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
         h1 = pow(0.01 / der12, 1.0 / 5.0);
     X.timestep[n] = fmin(100.0 * h, h1);
     X.facold[n] = 1.0e-4;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Particles on several slabs (fcpt_particles_slabs): particles::move()'s hand-over to the radial neighbours
+// (particles/particles.cpp:2033-2161).  Every slab holds every slot, so a record carries its slot index and the receiver
+// searches nothing.  A message is M.inner / M.outer: word 0 the record count as a double, then M.rec doubles per record.
+//
+// k_particles_emigrate: one lane per slot.  A live particle with d^2 < lo_sq leaves inwards, with d^2 > hi_sq outwards
+// (:2067, :2126; on an edge it stays).  Per side the wavefront's leavers are found with one ballot, the first of them adds
+// their number to the side's counter with ONE atomic, and every leaver takes its place from the lanes below it (mbcnt).
+// A leaver whose place is beyond the capacity stays, alive, for the next call; k_particles_emigrate_finish counts it.
+// No lane returns ahead of the ballots.  The order of the records is that of the atomics' arrival: not deterministic, and
+// it need not be, the receiver scatters by slot.
+__device__ __forceinline__ void particle_record_write(double *rec, int n, const ParticleArgs &A, const ParticleAdaptive &X, int nrec)
+{
+    rec[0] = (double)n;
+    rec[1] = A.r[n];
+    rec[2] = A.phi[n];
+    rec[3] = A.r_dot[n];
+    rec[4] = A.phi_dot[n];
+    rec[5] = A.stokes[n];
+    if (nrec == PARTICLE_RECORD_MAX) {
+        rec[6] = X.timestep[n];
+        rec[7] = X.facold[n];
+        rec[8] = X.r_ddot[n];
+        rec[9] = X.phi_ddot[n];
+    }
+}
+
+__global__ void __launch_bounds__(256) k_particles_emigrate(const ParticleArgs A, const ParticleAdaptive X, const ParticleMigrate M)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    int side = -1;
+    if (n < A.n && A.alive[n]) {
+        const double q1 = A.r[n];
+        double d2 = q1 * q1;
+        if (M.cartesian) {
+            const double q2 = A.phi[n];
+            d2 = q1 * q1 + q2 * q2;
+        }
+        if (M.has_inner && d2 < M.lo_sq)
+            side = 0;
+        else if (M.has_outer && d2 > M.hi_sq)
+            side = 1;
+    }
+    for (int s = 0; s < 2; ++s) {
+        const unsigned long long leavers = __builtin_amdgcn_ballot_w64(side == s);
+        if (leavers == 0) // (wave-uniform)
+            continue;
+        double *msg = s == 0 ? M.inner : M.outer;
+        const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(leavers >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)leavers, 0u));
+        unsigned base = 0;
+        if (side == s && below == 0) // the first leaver of the wavefront
+            base = atomicAdd(&M.cnt[s], (unsigned)__popcll(leavers));
+        base = __shfl(base, __ffsll((long long)leavers) - 1);
+        const unsigned place = base + below;
+        if (side == s && msg && place < (unsigned)M.capacity) {
+            particle_record_write(msg + 1 + (size_t)place * M.rec, n, A, X, M.rec);
+            A.alive[n] = 0;
+        }
+    }
+}
+
+// one lane, behind k_particles_emigrate: the clipped counts into word 0 of the messages, the totals, the counters back to 0
+__global__ void k_particles_emigrate_finish(const ParticleMigrate M)
+{
+    for (int s = 0; s < 2; ++s) {
+        double *msg = s == 0 ? M.inner : M.outer;
+        const unsigned found = M.cnt[s];
+        const unsigned sent = !msg ? 0u : (found < (unsigned)M.capacity ? found : (unsigned)M.capacity);
+        if (msg)
+            msg[0] = (double)sent;
+        M.tot[s] += sent;
+        M.tot[3] += found - sent;
+        M.cnt[s] = 0;
+    }
+}
+
+// k_particles_immigrate: blockIdx.y is the side; the count comes from word 0 on the device.  Lane t < count scatters record
+// t into its slot and sets alive.  A count that is no whole number in 0 .. capacity, or a slot index that is none in
+// 0 .. n-1, writes nothing of that message / record and goes to the status word (PARTICLE_GUARD_MESSAGE).
+__global__ void __launch_bounds__(256) k_particles_immigrate(const ParticleArgs A, const ParticleAdaptive X, const ParticleMigrate M)
+{
+    const double *msg = blockIdx.y == 0 ? M.inner : M.outer;
+    if (!msg)
+        return;
+    const unsigned t = blockIdx.x * 256 + threadIdx.x;
+    const double cnt = msg[0];
+    if (!(cnt >= 0.0 && cnt <= (double)M.capacity && cnt == floor(cnt))) { // (a NaN compares false)
+        if (t == 0)
+            *A.status = (unsigned long long)PARTICLE_GUARD_MESSAGE | ((unsigned long long)0xffffffffu << 8);
+        return;
+    }
+    const unsigned count = (unsigned)cnt;
+    if (t == 0 && count)
+        atomicAdd(&M.tot[2], (unsigned long long)count);
+    if (t >= count)
+        return;
+    const double *rec = msg + 1 + (size_t)t * M.rec;
+    const double slot = rec[0];
+    if (!(slot >= 0.0 && slot < (double)A.n && slot == floor(slot))) {
+        *A.status = (unsigned long long)PARTICLE_GUARD_MESSAGE | ((unsigned long long)0xffffffffu << 8);
+        return;
+    }
+    const int n = (int)slot;
+    A.r[n] = rec[1];
+    A.phi[n] = rec[2];
+    A.r_dot[n] = rec[3];
+    A.phi_dot[n] = rec[4];
+    A.stokes[n] = rec[5];
+    if (M.rec == PARTICLE_RECORD_MAX) {
+        X.timestep[n] = rec[6];
+        X.facold[n] = rec[7];
+        X.r_ddot[n] = rec[8];
+        X.phi_ddot[n] = rec[9];
+    }
+    A.alive[n] = 1;
 }

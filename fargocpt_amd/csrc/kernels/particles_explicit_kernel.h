@@ -1,6 +1,7 @@
 // k_particles_step_explicit (PARTICLES_DEV false: dt and frame_angle are kernel arguments) and
 // k_particles_step_explicit_clock (true: they come from the device clock), see particles.h, which includes this file once
-// for each with PARTICLES_KERNEL and PARTICLES_DEV defined.
+// for each with PARTICLES_KERNEL, PARTICLES_DEV and PARTICLES_SLAB defined (k_particles_step_explicit_slab: one of several
+// slabs, see particle_rinf_id and particle_off_slab).
 template <bool ADI, bool DRAG, bool CART>
 __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
     PARTICLES_KERNEL(const Dev P, const ParticleArgs A, const ParticleAdaptive X)
@@ -31,7 +32,8 @@ __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
         const double r = CART ? sqrt(q1 * q1 + q2 * q2) : q1;
         const double phi = CART ? particle_angle_cart(q1, q2) : q2;
         if (!((r < X.rmin) || (r > X.rmax))) { // RMIN, RMAX: inside [Rinf[0], Rinf[nr]]
-            const ParticleGasAt g = particle_interpolate<ADI>(P, A, r, phi);
+            const ParticleGasAt g = particle_interpolate<ADI, PARTICLES_SLAB>(P, A, r, phi);
+            const bool off_slab = particle_off_slab<PARTICLES_SLAB>(P, g.ib_raw, 0, nr - 3);
             double vrel_1, vrel_2, s = 0.0, c = 1.0;
             if (CART) {
                 sincos(phi, &s, &c);
@@ -48,6 +50,7 @@ __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
             int guard = particle_calc_tstop(A, A.radius[n], g.rho, vrel, g.temperature, tstop);
             if (!guard && tstop < 10.0 * dt)
                 guard = PARTICLE_GUARD_STIFF;
+            guard = particle_guard<PARTICLES_SLAB>(off_slab, guard);
             if (guard) {
                 *A.status = (unsigned long long)guard | ((unsigned long long)n << 8);
                 return;
@@ -79,10 +82,11 @@ __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
     bool last = false, reject = false;
     unsigned int accepted = 0, rejected = 0;
     const unsigned int cap = (unsigned int)X.max_attempts;
+    bool off_substep = false; // guard 11 (PARTICLES_SLAB): a substep's cell beyond the slab's rings; leaves with guard 9's branch
     while (!last) {
         // guard 9: an integer comparison, which no NaN in h, err or the state can defeat
-        if (accepted + rejected >= cap) {
-            *A.status = (unsigned long long)PARTICLE_GUARD_ATTEMPTS | ((unsigned long long)n << 8);
+        if (accepted + rejected >= cap || (PARTICLES_SLAB && off_substep)) {
+            *A.status = (unsigned long long)particle_guard<PARTICLES_SLAB>(off_substep, PARTICLE_GUARD_ATTEMPTS) | ((unsigned long long)n << 8);
             return;
         }
         double ts = h; // timestep; h is particles[i].timestep, which old_timestep aliases (:1726)
@@ -97,8 +101,9 @@ __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
         {
             const double r = CART ? sqrt(q1 * q1 + q2 * q2) : q1;
             const double phi = CART ? particle_angle_cart(q1, q2) : q2;
-            const int ia = particle_rinf_id(Rinf, nr, A, r);
+            const int ia = particle_rinf_id<PARTICLES_SLAB>(Rinf, nr, A, r);
             int is = r >= Rmed[ia] ? ia : ia - 1; // get_rmed_id with the release build's clamp
+            off_substep = off_substep || particle_off_slab<PARTICLES_SLAB>(P, is, 0, nr - 3);
             is = is < 0 ? 0 : is;
             int ja = (int)floor(phi * P.invdphi);
             ja = ja < 0 ? 0 : (ja > nphi - 1 ? nphi - 1 : ja);
@@ -206,6 +211,10 @@ __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
         }
     }
 
+    if (PARTICLES_SLAB && off_substep) { // (the last substep's cell)
+        *A.status = (unsigned long long)PARTICLE_GUARD_OFF_SLAB | ((unsigned long long)n << 8);
+        return;
+    }
     // ---- move(): escaped particles leave; rotate(): the frame's turn over the step -----------------------------------
     const double rsq = CART ? q1 * q1 + q2 * q2 : q1 * q1;
     if (rsq > A.escape_max_sq || rsq < A.escape_min_sq)

@@ -66,6 +66,25 @@ class SlabSet:
             c.exchange_unpack(bufs[k - 1][1] if k > 0 else None,
                               bufs[k + 1][0] if k < n - 1 else None)
 
+    def migrate_particles(self):
+        """particles::move between slabs held in this process (host staging): every slab packs its leavers, the messages
+        change hands, every slab unpacks.  The slabs have opted in with particles_slabs()."""
+        n = len(self.ctxs)
+        if n < 2:
+            return
+        cnt = self.ctxs[0].particles_migrate_count()
+        bufs = [(np.zeros(cnt), np.zeros(cnt)) for _ in range(n)]
+        for k, c in enumerate(self.ctxs):
+            c.particles_migrate_pack(bufs[k][0] if k > 0 else None, bufs[k][1] if k < n - 1 else None)
+        for k, c in enumerate(self.ctxs):
+            c.particles_migrate_unpack(bufs[k - 1][1] if k > 0 else None,
+                                       bufs[k + 1][0] if k < n - 1 else None)
+
+    def merged_particles(self, adaptive: bool = False) -> dict:
+        """The slabs' particles_get() (with adaptive: and particles_adaptive_get()) as one dictionary, see merge_particles."""
+        return merge_particles([c.particles_get() for c in self.ctxs],
+                               [c.particles_adaptive_get() for c in self.ctxs] if adaptive else None)
+
     # -- reference call sequence ---------------------------------------------
     def calculate_timestep(self) -> float:
         g = self.global_cfl()
@@ -118,6 +137,19 @@ class SlabSet:
                 parts.append(a[lo:hi])
             out[name] = np.concatenate(parts, axis=0)
         return out
+
+
+def merge_particles(parts, adaptive=None, slot_of_id=None) -> dict:
+    """Merge the slabs' particles_get() dictionaries (and, entry for entry, their particles_adaptive_get()) into one in
+    ascending slot order.  `slot_of_id`: {id: slot} of the list handed to particles_set; without it the ids themselves
+    order the result, which is slot order whenever the list was given in ascending id order."""
+    out = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+    if adaptive is not None:
+        out.update({k: np.concatenate([a[k] for a in adaptive]) for k in adaptive[0]})
+    ids = out["id"]
+    key = ids if slot_of_id is None else np.array([slot_of_id[int(i)] for i in ids], dtype=np.int64)
+    order = np.argsort(key, kind="stable")
+    return {k: v[order] for k, v in out.items()}
 
 
 class CircularOrbits:

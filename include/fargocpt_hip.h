@@ -454,7 +454,8 @@ int fcpt_recalculate_derived(fcpt_ctx *ctx);
 
 /* ---- Lagrangian dust particles with gas drag and diffusion ---------------------------------------------------------------
  * particles::integrate with ParticleIntegrator: midpoint (integrate_exponential_midpoint, src/particles/
- * particles.cpp:1579-1672, after Zhu et al. 2014 and Mignone et al. 2019) on one radial slab, for the host-stepped
+ * particles.cpp:1579-1672, after Zhu et al. 2014 and Mignone et al. 2019) on one radial slab (on several: see
+ * fcpt_particles_slabs, below), for the host-stepped
  * loop: per step fcpt_set_bodies, fcpt_particles_step, fcpt_step, fcpt_post -- the particle step reads the gas at the
  * start of the hydro step, where the reference calls it (src/simulation.cpp:177-180).  fcpt_run_steps advances
  * particles only after fcpt_particles_follow_run_steps(ctx, 1), below.  A context that never receives particles launches
@@ -465,8 +466,8 @@ int fcpt_recalculate_derived(fcpt_ctx *ctx);
  * from the last two rows, the mirror of the release build's behaviour below Rmed[0]) and that of v_r to [0, Nr-1].
  * ParticleIntegrator: explicit (integrate_explicit_adaptive, :1677-2014) with its CartesianParticles state is selected
  * with fcpt_particles_integrator, below; the host driver does not offer it yet and still refuses the key.
- * Not covered (the host driver refuses setups that ask for them): disk gravity on particles, leapfrog, several
- * slabs. */
+ * Not covered (the host driver refuses setups that ask for them): disk gravity on particles, leapfrog, particles on
+ * several slabs inside fcpt_run_steps or in the host driver. */
 typedef struct fcpt_particle_params {
     double particle_density;  /* ParticleDensity (code units) */
     double molecule_mass;     /* mu * m_u (code units), calc_tstop's m0 (particles.cpp:1139) */
@@ -486,8 +487,8 @@ int fcpt_particle_params_default(const fcpt_desc *d, fcpt_particle_params *out);
 /* Replace the particles of the context by n particles (host arrays of n entries each, copied; the caller's order is
  * kept: slot k holds particle k).  r, phi: position; r_dot, phi_dot: dr/dt and dphi/dt; radius: grain radius;
  * stokes: the Stokes number of the previous step (enters the smoothing length, particles.cpp:896-912; check_tstop's
- * value at the start).  n = 0 removes them.  FCPT_EINVAL: a context that is one of several slabs, escape radii
- * outside [rmin, rmax] or not ordered, a null array.  Blocks. */
+ * value at the start).  n = 0 removes them.  FCPT_EINVAL: a context that is one of several slabs and has not opted in
+ * with fcpt_particles_slabs, escape radii outside [rmin, rmax] or not ordered, a null array.  Blocks. */
 int fcpt_particles_set(fcpt_ctx *ctx, const fcpt_particle_params *params, int64_t n, const uint64_t *id, const double *r,
                        const double *phi, const double *r_dot, const double *phi_dot, const double *radius,
                        const double *stokes);
@@ -611,6 +612,65 @@ int fcpt_particles_adaptive_get(fcpt_ctx *ctx, int64_t capacity, double *timeste
  * on allocates, launches and computes what it did before. */
 int fcpt_particles_follow_run_steps(fcpt_ctx *ctx, int32_t on);
 int fcpt_particles_follow_run_steps_get(const fcpt_ctx *ctx, int32_t *on);
+
+/* ---- particles on several radial slabs: ownership and migration (particles::move, src/particles/particles.cpp:2016-2161)
+ * Opt-in with fcpt_particles_slabs {on = 1}; without it fcpt_particles_set on one of several slabs is refused as before.
+ *
+ * Ownership.  Every slab is handed the SAME full list by fcpt_particles_set and holds all n slots (slot k is particle k
+ * on every slab, about 57 bytes per particle and slab), but steps only the particles it owns: alive[k] is set where
+ * r_lo^2 <= d^2 < r_hi^2, d^2 = r^2 (x^2 + y^2 with cartesian = 1) and [r_lo, r_hi] the window of
+ * fcpt_particles_slab_window: Rinf of local row FCPT_OVERLAP and of local row nr - FCPT_OVERLAP (local_r_min /
+ * local_r_max of particles.cpp:527-529), -inf on the first and +inf on the last slab (at the grid's own edges the escape
+ * radii act first).  Neighbouring slabs return the same bits at their shared edge.  Needs no GPU.
+ *
+ * Migration.  After fcpt_particles_step a live owned particle with d^2 < r_lo^2 goes to the inner neighbour, one with
+ * d^2 > r_hi^2 to the outer one (:2067, :2126; exactly on an edge it stays): its alive byte is cleared by the sender and
+ * set by the receiver.  A record is the slot index followed by r, phi, r_dot, phi_dot, stokes and, once the explicit
+ * integrator's step sizes exist (they must then exist on every slab), timestep, facold, r_ddot, phi_ddot: R = 6 or 10
+ * doubles; id and radius are replicated and do not travel, the substep counters of fcpt_particles_adaptive_get stay with
+ * the slab that took the step.  A migration message is always exactly fcpt_exchange_count doubles long: word 0 holds the
+ * record count (as a double), the records follow, the rest is unspecified -- so the communicator of the ghost rings
+ * carries it unchanged.  migrate_capacity records per side and call; 0 selects the built-in (fcpt_exchange_count - 1) / R,
+ * a larger value is FCPT_EINVAL (when given, and again when the records grow to 10 doubles: the capacity in force is
+ * the smaller).  A particle beyond the capacity stays with its owner, alive, and is counted in `deferred`: the overlap
+ * rings still hold its gas, and the next call takes it.
+ *   fcpt_particles_migrate_pack / _unpack / _count mirror fcpt_exchange_pack / _unpack / _count (host or device buffers
+ *   of _count doubles, NULL skips a side): slabs of one process hand the messages over themselves.  _unpack reads the
+ *   count on the device and scatters by slot index; a record whose slot index is not in 0 .. n-1, or a count beyond the
+ *   capacity, writes nothing and is reported by the next blocking particle call ("guard 12").
+ *   fcpt_particles_migrate is the collective: pack, the neighbour exchange of the context's communicator on the
+ *   context's stream, unpack (blocks with the host link, stream-ordered with RCCL).  FCPT_EINVAL without a communicator
+ *   or without on.
+ * The per-slot state is a function of the inputs alone, so the slabs' states merged by slot carry the bits of a one-slab
+ * run on the same gas.  fcpt_particles_get / _count / _adaptive_get / _normals return the owned live particles in
+ * ascending slot order; the caller merges the slabs and sums counts (fcpt_allreduce_sum).
+ *
+ * Guard 11.  On a slab the step reports a particle that needs a gas row beyond the slab's rings on a side that has a
+ * neighbour (it moved more than the overlap in one step, or was deferred too long), where a one-slab run would read
+ * real gas and the clamps of the cell search would extrapolate silently: the lower row of a cell-centred interpolation
+ * or of the smoothing cell is below 0 or above nr - 3 (v_r is read up to two rows above it, and its row nr is not part
+ * of the ghost exchange), or the row of the diffusion kick is below 1 or above nr - 2.  As with guards 1 .. 10 nothing of
+ * the particle is written and the id and the guard come back at the next blocking call.  The clamps at the grid's own
+ * inner and outer edge are unchanged.
+ *
+ * fcpt_run_steps with fcpt_particles_follow_run_steps on returns FCPT_EINVAL on a context that is one of several slabs
+ * (*nsteps_done = 0, the clock untouched, nothing queued): particles inside the multi-slab device loop are not covered,
+ * nor does the host driver run particles with --ranks.
+ * sent_inner, sent_outer, received, deferred are running totals since fcpt_create, read-only (fcpt_particles_slabs
+ * ignores them); fcpt_particles_slabs_get blocks.  The setting belongs to the context and outlives fcpt_particles_set;
+ * switch it before fcpt_particles_set. */
+typedef struct fcpt_particle_slabs {
+    int32_t on;               /* 1: this context takes particles as one of several slabs */
+    int32_t migrate_capacity; /* records per side and call, 0: built-in */
+    uint64_t sent_inner, sent_outer, received, deferred;
+} fcpt_particle_slabs;
+int fcpt_particles_slab_window(const fcpt_desc *d, const double *radii, double window[2]);
+int fcpt_particles_slabs(fcpt_ctx *ctx, const fcpt_particle_slabs *p);
+int fcpt_particles_slabs_get(fcpt_ctx *ctx, fcpt_particle_slabs *out);
+int fcpt_particles_migrate_count(fcpt_ctx *ctx, uint64_t *count);
+int fcpt_particles_migrate_pack(fcpt_ctx *ctx, double *send_inner, double *send_outer);
+int fcpt_particles_migrate_unpack(fcpt_ctx *ctx, const double *recv_inner, const double *recv_outer);
+int fcpt_particles_migrate(fcpt_ctx *ctx);
 
 /* The generator itself, on the host (no GPU needed): ten rounds of Philox4x32, and the deviate above. */
 void fcpt_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
