@@ -153,7 +153,7 @@ def merge_particles(parts, adaptive=None, slot_of_id=None) -> dict:
 
 
 class CircularOrbits:
-    """The N-body stand-in of the host driver (csrc/host/fargocpt_hip_main.cpp, set_bodies): the star at the origin,
+    """The N-body stand-in of the host driver (csrc/host/bodies.cpp, BodySystem::set_circular): the star at the origin,
     every planet on its initial circular orbit seen in the frame rotating with OmegaFrame, its mass ramped up as
     t_planet::get_rampup_mass does (nbody/planet.cpp:166-179), and the indirect term of the star-centred frame
     without the disk (refframe::IndirectTermPlanets, frame_of_reference.cpp:138-160: minus the star's velocity
