@@ -352,6 +352,7 @@ class Context:
         lib.check(lib.fn("create")(C.byref(self.desc), _as_dp(radii), C.byref(self._h)), "create")
         self.split = Split()
         lib.check(lib.fn("get_split")(self._h, C.byref(self.split)), "get_split")
+        self.host_link: Optional[str] = None    # the path of comm_init_host while that communicator stands
         self.nr, self.nphi = self.split.nr, d.nphi
 
     def close(self):
@@ -447,12 +448,14 @@ class Context:
     def comm_init_host(self, path: str):
         """The host-staged transport (several slabs on one GPU): a shared-memory file instead of RCCL."""
         self._call("comm_init_host", C.c_char_p(path.encode()))
+        self.host_link = path
 
     def comm_barrier(self):
         self._call("comm_barrier")
 
     def comm_destroy(self):
         self._call("comm_destroy")
+        self.host_link = None
 
     def exchange(self):
         self._call("exchange")
@@ -585,7 +588,9 @@ class Context:
         return out
 
     def particles_follow_run_steps(self, on: bool = True):
-        """run_steps also takes the particle step of every iteration (device-resident dt, frame angle and counter)."""
+        """run_steps also takes the particle step of every iteration (device-resident dt, frame angle and counter).
+        On one of several slabs the context needs a communicator (comm_init / comm_init_host) and particles_slabs(True):
+        every iteration then steps the slab's particles and hands the leavers to the neighbours (see run_steps)."""
         self._call("particles_follow_run_steps", _i32(int(bool(on))))
 
     def particles_follow_run_steps_get(self) -> bool:
@@ -715,6 +720,13 @@ class Context:
         return {n: (ms[k], cnt[k]) for k, n in enumerate(names) if cnt[k] > 0}
 
     def run_steps(self, nsteps: int, snap: bool = False) -> int:
+        """fcpt_run_steps: `nsteps` iterations of sim::run's loop, the step length staying on the device unless `snap`
+        (monitor-time snapping) is set; -> the steps taken.  With a communicator every slab calls it with the same
+        arguments (one thread or process per slab, see driver.SlabSet.run_steps_linked).
+        With particles_follow_run_steps an iteration is: CFL [all-reduce], time-step policy, particle step, [migration:
+        pack, neighbour exchange, unpack,] gas step, [ghost exchange,] post.  On several slabs the migration is issued in
+        every iteration, also without particles, with messages of 1 + capacity * record length doubles; it is refused
+        (FcptError, clock untouched) without a communicator or without particles_slabs(True)."""
         done = C.c_int64()
         self._call("run_steps", C.c_int64(nsteps), _i32(1 if snap else 0), C.byref(done))
         return done.value

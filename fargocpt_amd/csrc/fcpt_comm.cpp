@@ -132,6 +132,7 @@ struct alignas(64) LinkHeader {
 struct alignas(64) LinkMailboxHead {
     uint64_t written; // sequence number of the message in `data`
     uint64_t read;    // ... of the last message the owner has taken out
+    uint64_t count;   // doubles of the message in `data` (written ahead of `written`): the receiver expects as many
 };
 struct alignas(64) LinkSlot {
     uint64_t seq;
@@ -375,8 +376,14 @@ int link_exchange(Comm *c, int peer_inner, const double *send_inner, double *rec
                   const double *send_outer, double *recv_outer, size_t count, hipStream_t st)
 {
     HostLink *h = c->host;
-    if (count != h->count || peer_inner == c->rank || peer_outer == c->rank) {
-        set_error("host-staged transport: message of %zu doubles on a link of %zu (or a slab that is its own neighbour)", count, h->count);
+    // (a mailbox holds the ghost rings' count; the particle messages of fcpt_run_steps are shorter, and equally long on
+    //  both ends)
+    if (count == 0 || count > h->count) {
+        set_error("host-staged transport: a message of %zu doubles, the link carries 1 .. %zu", count, h->count);
+        return FCPT_EINVAL;
+    }
+    if (peer_inner == c->rank || peer_outer == c->rank) {
+        set_error("host-staged transport: slab %d is its own neighbour", c->rank);
         return FCPT_EINVAL;
     }
     const size_t nb = count * sizeof(double);
@@ -402,6 +409,7 @@ int link_exchange(Comm *c, int peer_inner, const double *send_inner, double *rec
         if (!link_wait(h, &b->read, s - 1, "ghost exchange (send)"))
             return FCPT_ECOMM;
         std::memcpy(h->box_data(peers[k], 1 - k), sends[k], nb);
+        b->count = count;
         __atomic_store_n(&b->written, s, __ATOMIC_RELEASE);
     }
     double *recvs[2] = {r_in, r_out};
@@ -411,6 +419,12 @@ int link_exchange(Comm *c, int peer_inner, const double *send_inner, double *rec
         LinkMailboxHead *b = h->box(c->rank, k);
         if (!link_wait(h, &b->written, s, "ghost exchange (receive)"))
             return FCPT_ECOMM;
+        if (b->count != count) { // the two ends disagree on the length: nothing of the mailbox is taken
+            set_error("host-staged transport: slab %d sent message %llu with %llu doubles, slab %d expects %zu (record length "
+                      "and capacity of the particle messages must be equal on all slabs)",
+                      peers[k], (unsigned long long)s, (unsigned long long)b->count, c->rank, count);
+            return FCPT_ECOMM;
+        }
         std::memcpy(recvs[k], h->box_data(c->rank, k), nb);
         __atomic_store_n(&b->read, s, __ATOMIC_RELEASE);
     }

@@ -131,7 +131,7 @@ struct fcpt_ctx {
     unsigned long long *part_step_offset = nullptr;
     // fcpt_particles_slabs (outlives fcpt_particles_set): the setting (its four totals live on the device: part_mtot), the
     // ownership window, and -- made when first switched on -- the messages [send inner, send outer, recv inner, recv
-    // outer] of fcpt_exchange_count doubles each and the two per-call counters of k_particles_emigrate
+    // outer] of fcpt_exchange_count doubles each and the per-call counts of the emigration (ParticleMigrate::cnt)
     fcpt_particle_slabs part_slabs = {0, 0, 0, 0, 0, 0};
     double part_window[2] = {0.0, 0.0};
     double *part_mbuf[4] = {};
@@ -211,6 +211,8 @@ void particles_free(fcpt_ctx *c);
 int particles_loop_check(const fcpt_ctx *c);
 void particles_loop_launch(const fcpt_ctx *c, ParticleLaunch *L);
 void enqueue_particles_loop(fcpt_ctx *c);
+bool particles_loop_migrates(const fcpt_ctx *c);
+int enqueue_particles_migrate(fcpt_ctx *c);
 // fcpt_exchange.hip
 int enqueue_exchange(fcpt_ctx *c);
 int enqueue_cfl_allreduce(fcpt_ctx *c);

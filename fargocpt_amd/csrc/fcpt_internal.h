@@ -306,6 +306,7 @@ struct ParticleArgs {
 // fcpt_particles_slabs: what k_particles_emigrate / k_particles_immigrate need besides the arrays (kernels/particles.h)
 #define PARTICLE_RECORD_MIN 6  // slot, r, phi, r_dot, phi_dot, stokes
 #define PARTICLE_RECORD_MAX 10 // ... timestep, facold, r_ddot, phi_ddot
+#define PARTICLE_MIGRATE_GROUPS 1024 // workgroups of an emigration at the most: the slots are dealt out in equal stretches
 struct ParticleMigrate {
     double lo_sq, hi_sq;      // squared edges of the ownership window (-inf / +inf without a neighbour on that side)
     int has_inner, has_outer; // this edge has a neighbour
@@ -313,8 +314,10 @@ struct ParticleMigrate {
     int capacity;             // records per side and call
     int rec;                  // doubles per record: PARTICLE_RECORD_MIN, or _MAX with the adaptive arrays
     double *inner, *outer;    // the two messages (null: that side is skipped)
-    unsigned int *cnt;        // [2]: particles selected for the inner / outer side in this call (zero between calls)
+    unsigned int *cnt;        // [2][PARTICLE_MIGRATE_GROUPS + 1]: per side the leavers of each workgroup of the call, then
+                              // their running sums (kernels/particles.h); rewritten by every call
     unsigned long long *tot;  // [4]: sent_inner, sent_outer, received, deferred since fcpt_create
+    int chunk, groups;        // set by launch_particles_emigrate: slots per workgroup (a multiple of 256), workgroups
 };
 
 // the per-particle state of the explicit adaptive integrator (k_particles_step_explicit): a second device block,

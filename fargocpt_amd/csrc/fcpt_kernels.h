@@ -23,7 +23,8 @@ enum KernelId {
     KID_TRANSPORT_FUSED, KID_MASSFLOW, KID_CFL_RINGS, KID_THETA_GATED_BOUNDARY, KID_EXCHANGE_COPY,
     KID_DISK_ON_BODY, KID_VISC_FACTORS, KID_SOURCE_MARCH_ADI, KID_SOURCE_MARCH_ADI_WIDE,
     KID_ACCEL_ON_GAS, KID_SOURCE_MARCH_ADI_ACC, KID_TRANSPORT_RADIAL_MEANS, KID_CFL_RINGS_BC,
-    KID_DISK_ON_BODIES, KID_PARTICLES, KID_PARTICLES_EXPLICIT, KID_COUNT
+    KID_DISK_ON_BODIES, KID_PARTICLES, KID_PARTICLES_EXPLICIT, KID_PARTICLES_EMIGRATE, KID_PARTICLES_EMIGRATE_FINISH,
+    KID_PARTICLES_IMMIGRATE, KID_PARTICLES_EMIGRATE_COUNT, KID_COUNT
 };
 static_assert(KID_COUNT <= 64, "fcpt_profile_start selects kernels with a 64-bit mask");
 extern const char *const kKernelNames[KID_COUNT];

@@ -161,6 +161,7 @@ void migrate_args(const fcpt_ctx *c, double *inner, double *outer, ParticleMigra
     M->outer = M->has_outer ? outer : nullptr;
     M->cnt = c->part_mcnt;
     M->tot = c->part_mtot;
+    M->chunk = M->groups = 0; // (launch_particles_emigrate's)
 }
 bool buffer_on_device(const void *p)
 {
@@ -232,6 +233,24 @@ int migrate_unpack(fcpt_ctx *c, const double *recv_inner, const double *recv_out
         HIPCHK(hipStreamSynchronize(c->stream)); // the caller's host buffers are free again
     return FCPT_OK;
 }
+// pack, the neighbour exchange of the ghost rings' communicator with the messages in its place, unpack: one stream.
+// `count`: the doubles that travel per message, word 0 and the records the capacity allows at the least
+int migrate_collective(fcpt_ctx *c, size_t count)
+{
+    double *s_in = c->peer_inner >= 0 ? c->part_mbuf[0] : nullptr, *s_out = c->peer_outer >= 0 ? c->part_mbuf[1] : nullptr;
+    double *r_in = c->peer_inner >= 0 ? c->part_mbuf[2] : nullptr, *r_out = c->peer_outer >= 0 ? c->part_mbuf[3] : nullptr;
+    if (c->part.n <= 0) { // the neighbours still wait for this slab's messages: empty ones
+        for (double *m : {s_in, s_out})
+            if (m)
+                HIPCHK(hipMemsetAsync(m, 0, sizeof(double), c->stream));
+    } else if (int rc = migrate_pack(c, s_in, s_out)) {
+        return rc;
+    }
+    const int rc = comm_neighbour_exchange(c->comm, c->peer_inner, s_in, r_in, c->peer_outer, s_out, r_out, count, c->stream);
+    if (rc)
+        return rc == FCPT_EHIP ? FCPT_ECOMM : rc;
+    return migrate_unpack(c, r_in, r_out);
+}
 
 } // namespace
 
@@ -242,9 +261,11 @@ int particles_loop_check(const fcpt_ctx *c)
 {
     if (!c->part_follow)
         return FCPT_OK;
-    if (c->d.nranks > 1) {
-        set_error("fcpt_run_steps: fcpt_particles_follow_run_steps is on, and particles inside the multi-slab loop are not "
-                  "covered (this context is slab %d of %d): step them with fcpt_particles_step and fcpt_particles_migrate",
+    if (c->d.nranks > 1 && (!c->comm || !c->part_slabs.on)) {
+        set_error("fcpt_run_steps: fcpt_particles_follow_run_steps is on, and particles inside the multi-slab loop need %s%s%s "
+                  "(this context is slab %d of %d)",
+                  c->comm ? "" : "a communicator (fcpt_comm_init or fcpt_comm_init_host)",
+                  !c->comm && !c->part_slabs.on ? " and " : "", c->part_slabs.on ? "" : "fcpt_particles_slabs with on = 1",
                   c->d.rank, c->d.nranks);
         return FCPT_EINVAL;
     }
@@ -295,6 +316,7 @@ void particles_loop_launch(const fcpt_ctx *c, ParticleLaunch *L)
 }
 
 // the particle step of one iteration of fcpt_run_steps' device loop, behind the launch that left the step length in the clock
+// (one of several slabs: the clock-reading slab kernels)
 void enqueue_particles_loop(fcpt_ctx *c)
 {
     ParticleLaunch L;
@@ -303,9 +325,24 @@ void enqueue_particles_loop(fcpt_ctx *c)
         return;
     join_side(c);
     if (L.explicit_adaptive)
-        launch_particles_explicit(c->P, L.A, L.X, L.cartesian != 0, c->stream);
+        launch_particles_explicit(c->P, L.A, L.X, L.cartesian != 0, c->stream, on_slab(c));
     else
-        launch_particles(c->P, L.A, c->stream);
+        launch_particles(c->P, L.A, c->stream, on_slab(c));
+}
+
+// fcpt_run_steps on several slabs hands the step's leavers over with this (follow on, fcpt_particles_slabs on, a
+// communicator: particles_loop_check); also with no particles at all, so that every slab makes the same calls
+bool particles_loop_migrates(const fcpt_ctx *c)
+{
+    return c->part_follow && on_slab(c) && c->comm;
+}
+
+// The migration of one iteration of the multi-slab device loop, on the context's stream: fcpt_particles_migrate with
+// messages cut to what the capacity in force can fill, 1 + capacity * R doubles (equal on all slabs: migrate_capacity and
+// the record length are)
+int enqueue_particles_migrate(fcpt_ctx *c)
+{
+    return migrate_collective(c, 1 + (size_t)migrate_capacity(c) * (size_t)record_doubles(c));
 }
 
 } // namespace fcpt
@@ -762,7 +799,7 @@ int fcpt_particles_slabs(fcpt_ctx *c, const fcpt_particle_slabs *p)
         for (int k = 0; k < 4; ++k)
             if (int rc = dev_alloc(c, &c->part_mbuf[k], message_doubles(c)))
                 return rc;
-        if (int rc = dev_alloc(c, &c->part_mcnt, 2))
+        if (int rc = dev_alloc(c, &c->part_mcnt, 2 * (PARTICLE_MIGRATE_GROUPS + 1)))
             return rc;
         if (int rc = dev_alloc(c, &c->part_mtot, 4))
             return rc;
@@ -810,7 +847,7 @@ int fcpt_particles_migrate_unpack(fcpt_ctx *c, const double *recv_inner, const d
     return migrate_unpack(c, recv_inner, recv_outer);
 }
 
-// pack, the neighbour exchange of the ghost rings' communicator with the messages in its place, unpack: one stream
+// the collective with messages of the documented full length, fcpt_particles_migrate_count
 int fcpt_particles_migrate(fcpt_ctx *c)
 {
     if (int rc = migrate_check(c, "fcpt_particles_migrate"))
@@ -820,20 +857,7 @@ int fcpt_particles_migrate(fcpt_ctx *c)
         return FCPT_EINVAL;
     }
     ProfScope prof_scope(c);
-    double *s_in = c->peer_inner >= 0 ? c->part_mbuf[0] : nullptr, *s_out = c->peer_outer >= 0 ? c->part_mbuf[1] : nullptr;
-    double *r_in = c->peer_inner >= 0 ? c->part_mbuf[2] : nullptr, *r_out = c->peer_outer >= 0 ? c->part_mbuf[3] : nullptr;
-    if (c->part.n <= 0) { // the neighbours still wait for this slab's messages: empty ones
-        for (double *m : {s_in, s_out})
-            if (m)
-                HIPCHK(hipMemsetAsync(m, 0, sizeof(double), c->stream));
-    } else if (int rc = migrate_pack(c, s_in, s_out)) {
-        return rc;
-    }
-    const int rc = comm_neighbour_exchange(c->comm, c->peer_inner, s_in, r_in, c->peer_outer, s_out, r_out, message_doubles(c),
-                                           c->stream);
-    if (rc)
-        return rc == FCPT_EHIP ? FCPT_ECOMM : rc;
-    return migrate_unpack(c, r_in, r_out);
+    return migrate_collective(c, message_doubles(c));
 }
 
 } // extern "C"

@@ -582,15 +582,32 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
     // iteration count to an offset left here, once, outside any graph), and the host's counter follows when the steps are
     // queued; the host-stepped branch calls fcpt_particles_step, which counts; without particles the counter still advances
     const bool follow = c->part_follow, follow_dev = follow && !slabs && !snap && c->part.n > 0;
-    if (follow_dev && nsteps > 0)
+    // ... on several slabs (particles_loop_check: a communicator and fcpt_particles_slabs): the step and the migration
+    const bool follow_slabs = slabs && particles_loop_migrates(c);
+    // set by the branches that call fcpt_particles_step, which counts every call, also one without particles
+    bool counted_by_particles_step = false;
+    if ((follow_dev || (follow_slabs && !snap && c->part.n > 0)) && nsteps > 0)
         launch_particles_counter_offset(c->part_step_offset, c->part_diff.step, c->P.clk, c->stream);
     if (slabs && !snap) {
-        // several slabs, dt never leaves the device: CFL -> MIN over the slabs (cfl.cpp:379) -> policy kernel -> step
-        // -> ghost exchange (simulation.cpp:236) -> post, all on one stream
+        // several slabs, dt never leaves the device: CFL -> MIN over the slabs (cfl.cpp:379) -> policy kernel
+        // [-> particle step -> migration] -> step -> ghost exchange (simulation.cpp:236) -> post, all on one stream
         for (; n < nsteps; ++n) {
             if (int rc = enqueue_cfl_allreduce(c))
                 return rc;
             launch_clock_policy_ptr(c->P.clk, c->d.cfl_max_var, c->d_cfl, c->stream);
+            if (follow_slabs) {
+                // the particle step where the reference has it (simulation.cpp:177-180), in its clock-reading slab form
+                // (none without particles), then particles::move's hand-over; every slab issues the collective in every
+                // iteration, with or without particles.
+                // The migration's neighbour exchange is queued on the context's stream, like the all-reduce above.  With
+                // comm_overlap the ghost exchange runs on the communication stream, and still no two calls of this
+                // communicator can overlap: the context's stream has waited for the previous ghost exchange (e_received,
+                // enqueue_exchange) before anything of this iteration, and the next ghost exchange waits for e_packed,
+                // which enqueue_exchange records on the context's stream behind this migration.
+                enqueue_particles_loop(c);
+                if (int rc = enqueue_particles_migrate(c))
+                    return rc;
+            }
             c->skip_q_store = c->d.integrator != FCPT_INTEGRATOR_LEAPFROG && n + 1 < nsteps; // Q+ / Q- (outputs) by the last step only
             enqueue_step(c, true, 0.0, c->d.cfl <= 0.8);
             if (int rc = enqueue_exchange(c))
@@ -615,6 +632,13 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
             if (int rc = fcpt_snap_to_monitor(c, dt, &step_dt))
                 return rc;
             const double time_next_monitor = (k.n_monitor + 1) * c->d.monitor_timestep;
+            if (follow_slabs) { // simulation.cpp:177-180 with the indirect term of the last fcpt_set_bodies, then particles::move
+                counted_by_particles_step = true;
+                if (int rc = fcpt_particles_step(c, step_dt, c->P.indirect_x, c->P.indirect_y, c->d.omega_frame * step_dt))
+                    return rc;
+                if (int rc = fcpt_particles_migrate(c))
+                    return rc;
+            }
             if (int rc = fcpt_step(c, step_dt))
                 return rc;
             if (int rc = fcpt_exchange(c))
@@ -684,9 +708,11 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
             if (int rc = fcpt_snap_to_monitor(c, dt, &step_dt))
                 return rc;
             const double time_next_monitor = (k.n_monitor + 1) * c->d.monitor_timestep;
-            if (follow) // simulation.cpp:177-180, with the indirect term of the last fcpt_set_bodies
+            if (follow) { // simulation.cpp:177-180, with the indirect term of the last fcpt_set_bodies
+                counted_by_particles_step = true;
                 if (int rc = fcpt_particles_step(c, step_dt, c->P.indirect_x, c->P.indirect_y, c->d.omega_frame * step_dt))
                     return rc;
+            }
             if (int rc = fcpt_step(c, step_dt))
                 return rc;
             if (int rc = fcpt_post(c, step_dt))
@@ -702,7 +728,7 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
             }
         }
     }
-    if (follow && (slabs || !snap))
+    if (follow && !counted_by_particles_step) // the loops that queue the step themselves, or none: one count per iteration
         c->part_diff.step += (unsigned long long)n;
     if (done)
         *done = n;

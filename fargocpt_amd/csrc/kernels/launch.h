@@ -13,7 +13,8 @@ const char *const kKernelNames[KID_COUNT] = {
     "k_transport_theta_march", "k_transport_fused", "k_massflow", "k_cfl_rings", "k_theta_march_gated_boundary",
     "k_exchange_copy", "k_disk_on_body", "k_visc_factors", "k_source_march_adi", "k_source_march_adi_wide",
     "k_accel_on_gas", "k_source_march_adi_acc",
-    "k_transport_radial_means", "k_cfl_rings_bc", "k_disk_on_bodies", "k_particles_step", "k_particles_step_explicit"};
+    "k_transport_radial_means", "k_cfl_rings_bc", "k_disk_on_bodies", "k_particles_step", "k_particles_step_explicit",
+    "k_particles_emigrate", "k_particles_emigrate_finish", "k_particles_immigrate", "k_particles_emigrate_count"};
 
 thread_local Profiler *g_prof = nullptr;
 
@@ -534,7 +535,8 @@ void launch_disk_on_bodies(const Dev &P, int n, const DiskBodies &B, double *par
 }
 
 // one lane per particle slot (dead slots return at once); the view's state grids are those of the start of the step
-// slab: the context is one of several slabs (fcpt_particles_slabs; host-argument form only: fcpt_run_steps refuses it)
+// slab: the context is one of several slabs (fcpt_particles_slabs), in either form: host arguments (fcpt_particles_step) or
+// the device clock (fcpt_run_steps on several slabs)
 void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st, bool slab)
 {
     if (A.n <= 0)
@@ -544,7 +546,10 @@ void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st, bool 
         with_bool(P.adiabatic, [&](auto ADI) {
             with_bool(A.gas_drag != 0, [&](auto DRAG) {
                 with_bool(A.diffusion != 0, [&](auto DIFF) {
-                    KLAUNCH(KID_PARTICLES, (k_particles_step<TARG(ADI), TARG(DRAG), TARG(DIFF), false, true>), grid, block, P, A);
+                    with_bool(A.step_offset != nullptr, [&](auto DEV) {
+                        KLAUNCH(KID_PARTICLES, (k_particles_step<TARG(ADI), TARG(DRAG), TARG(DIFF), TARG(DEV), true>), grid, block, P,
+                                A);
+                    });
                 });
             });
         });
@@ -571,7 +576,10 @@ void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const Partic
     with_bool(P.adiabatic, [&](auto ADI) {
         with_bool(A.gas_drag != 0, [&](auto DRAG) {
             with_bool(cartesian, [&](auto CART) {
-                if (slab)
+                if (slab && A.step_offset)
+                    KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit_slab_clock<TARG(ADI), TARG(DRAG), TARG(CART)>), grid,
+                            block, P, A, X);
+                else if (slab)
                     KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit_slab<TARG(ADI), TARG(DRAG), TARG(CART)>), grid, block, P,
                             A, X);
                 else if (A.step_offset)
@@ -604,19 +612,25 @@ void launch_particles_counter_offset(unsigned long long *offset, unsigned long l
     hipLaunchKernelGGL(k_particles_counter_offset, dim3(1), dim3(1), 0, st, offset, counter, clk);
 }
 
-// fcpt_particles_slabs: one lane per slot, then one lane for the counts; the receiver's grid covers the capacity of a side
-void launch_particles_emigrate(const ParticleArgs &A, const ParticleAdaptive &X, const ParticleMigrate &M, hipStream_t st)
+// fcpt_particles_slabs: the slots in at most PARTICLE_MIGRATE_GROUPS equal stretches of whole workgroup passes, counted,
+// summed by one workgroup and placed; the receiver's grid covers the capacity of a side
+void launch_particles_emigrate(const ParticleArgs &A, const ParticleAdaptive &X, const ParticleMigrate &M0, hipStream_t st)
 {
     if (A.n <= 0)
         return;
-    hipLaunchKernelGGL(k_particles_emigrate, dim3((A.n + 255) / 256), dim3(256), 0, st, A, X, M);
-    hipLaunchKernelGGL(k_particles_emigrate_finish, dim3(1), dim3(1), 0, st, M);
+    ParticleMigrate M = M0;
+    const int passes = ((A.n + 255) / 256 + PARTICLE_MIGRATE_GROUPS - 1) / PARTICLE_MIGRATE_GROUPS;
+    M.chunk = 256 * passes;
+    M.groups = (A.n + M.chunk - 1) / M.chunk;
+    KLAUNCH(KID_PARTICLES_EMIGRATE_COUNT, k_particles_emigrate_count, dim3(M.groups), dim3(256), A, M);
+    KLAUNCH(KID_PARTICLES_EMIGRATE_FINISH, k_particles_emigrate_finish, dim3(1), dim3(256), M);
+    KLAUNCH(KID_PARTICLES_EMIGRATE, k_particles_emigrate, dim3(M.groups), dim3(256), A, X, M);
 }
 void launch_particles_immigrate(const ParticleArgs &A, const ParticleAdaptive &X, const ParticleMigrate &M, hipStream_t st)
 {
     if (A.n <= 0 || M.capacity <= 0)
         return;
-    hipLaunchKernelGGL(k_particles_immigrate, dim3((M.capacity + 255) / 256, 2), dim3(256), 0, st, A, X, M);
+    KLAUNCH(KID_PARTICLES_IMMIGRATE, k_particles_immigrate, dim3((M.capacity + 255) / 256, 2), dim3(256), A, X, M);
 }
 
 // rings whose CFL terms read nothing the ghost exchange or the boundary kernels write: ring i reads rows i

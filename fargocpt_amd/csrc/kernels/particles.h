@@ -256,6 +256,9 @@ template <bool SLAB> __device__ __forceinline__ bool particle_off_slab(const Dev
 // form needs a name of its own, k_particles_step_explicit_clock, and a kernel of either name around a shared inlined body
 // costs two instances a wave per SIMD.  Its text therefore stands in kernels/particles_explicit_kernel.h, included once for
 // each name.  The clock is read ahead of the kernel's stores, through the scalar cache.
+// DEV and SLAB together (fcpt_run_steps on several slabs) are k_particles_step<., ., ., true, true> and
+// k_particles_step_explicit_slab_clock: the two departures touch different statements (the three scalars; the cell search
+// and guard 11), so the combination keeps the bits each of them keeps.
 template <bool DEV> __device__ __forceinline__ double particle_dt(const Dev &P, const ParticleArgs &A)
 {
     return DEV ? P.clk->dt : A.dt;
@@ -544,6 +547,14 @@ __device__ __forceinline__ void particle_accel(const Dev &P, const ParticleArgs 
 #undef PARTICLES_KERNEL
 #undef PARTICLES_DEV
 #undef PARTICLES_SLAB
+// ... and its clock form, for fcpt_run_steps on several slabs: both departures from the first name at once, nothing else
+#define PARTICLES_KERNEL k_particles_step_explicit_slab_clock
+#define PARTICLES_DEV true
+#define PARTICLES_SLAB true
+#include "particles_explicit_kernel.h"
+#undef PARTICLES_KERNEL
+#undef PARTICLES_DEV
+#undef PARTICLES_SLAB
 
 // init_particle_timestep (:248-374): Hairer's starting step with rsmooth = 0.05, facold = 1e-4
 template <bool CART> __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
@@ -609,12 +620,36 @@ template <bool CART> __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
 // (particles/particles.cpp:2033-2161).  Every slab holds every slot, so a record carries its slot index and the receiver
 // searches nothing.  A message is M.inner / M.outer: word 0 the record count as a double, then M.rec doubles per record.
 //
-// k_particles_emigrate: one lane per slot.  A live particle with d^2 < lo_sq leaves inwards, with d^2 > hi_sq outwards
-// (:2067, :2126; on an edge it stays).  Per side the wavefront's leavers are found with one ballot, the first of them adds
-// their number to the side's counter with ONE atomic, and every leaver takes its place from the lanes below it (mbcnt).
-// A leaver whose place is beyond the capacity stays, alive, for the next call; k_particles_emigrate_finish counts it.
-// No lane returns ahead of the ballots.  The order of the records is that of the atomics' arrival: not deterministic, and
-// it need not be, the receiver scatters by slot.
+// Emigration.  The leavers of a side are served in the order of their slots: a leaver's place in the message is the number of leavers of
+// that side in the slots below its own.  A leaver whose place is beyond the capacity stays, alive, for the next call, so
+// with more leavers than places the lowest slots go: which ones go depends on the particles alone, never on the order in
+// which wavefronts run, and two runs of one state send the same records in the same places.  Three launches:
+//   k_particles_emigrate_count   workgroup b takes the M.chunk slots from b * M.chunk on (a multiple of 256, so every lane
+//                                makes every pass and reaches every ballot) and stores its leavers per side, M.cnt[s][b]
+//   k_particles_emigrate_finish  one workgroup: M.cnt[s][0 .. groups] becomes the running sum in front of each workgroup
+//                                (the last entry the side's total); the clipped counts into word 0, the totals
+//   k_particles_emigrate         a leaver's place: the sum in front of its workgroup, the leavers of the workgroup's earlier
+//                                passes and of the wavefronts below in this pass, the lanes below it in the ballot (mbcnt).
+//                                A workgroup without leavers returns at once, without a read of the particles.
+// side of slot n: 0 leaves inwards (d^2 < lo_sq), 1 outwards (d^2 > hi_sq), -1 stays, is dead or is no slot
+// (particles.cpp:2067, :2126; on an edge it stays)
+__device__ __forceinline__ int particle_leaves(const ParticleArgs &A, const ParticleMigrate &M, int n)
+{
+    if (n >= A.n || !A.alive[n])
+        return -1;
+    const double q1 = A.r[n];
+    double d2 = q1 * q1;
+    if (M.cartesian) {
+        const double q2 = A.phi[n];
+        d2 = q1 * q1 + q2 * q2;
+    }
+    if (M.has_inner && d2 < M.lo_sq)
+        return 0;
+    if (M.has_outer && d2 > M.hi_sq)
+        return 1;
+    return -1;
+}
+
 __device__ __forceinline__ void particle_record_write(double *rec, int n, const ParticleArgs &A, const ParticleAdaptive &X, int nrec)
 {
     rec[0] = (double)n;
@@ -631,52 +666,99 @@ __device__ __forceinline__ void particle_record_write(double *rec, int n, const 
     }
 }
 
-__global__ void __launch_bounds__(256) k_particles_emigrate(const ParticleArgs A, const ParticleAdaptive X, const ParticleMigrate M)
+__global__ void __launch_bounds__(256) k_particles_emigrate_count(const ParticleArgs A, const ParticleMigrate M)
 {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    int side = -1;
-    if (n < A.n && A.alive[n]) {
-        const double q1 = A.r[n];
-        double d2 = q1 * q1;
-        if (M.cartesian) {
-            const double q2 = A.phi[n];
-            d2 = q1 * q1 + q2 * q2;
-        }
-        if (M.has_inner && d2 < M.lo_sq)
-            side = 0;
-        else if (M.has_outer && d2 > M.hi_sq)
-            side = 1;
+    __shared__ unsigned wave_found[2][4];
+    const int first = blockIdx.x * M.chunk;
+    unsigned found[2] = {0u, 0u}; // (wave-uniform)
+    for (int i = threadIdx.x; i < M.chunk; i += 256) {
+        const int side = particle_leaves(A, M, first + i);
+        found[0] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(side == 0));
+        found[1] += (unsigned)__popcll(__builtin_amdgcn_ballot_w64(side == 1));
     }
-    for (int s = 0; s < 2; ++s) {
-        const unsigned long long leavers = __builtin_amdgcn_ballot_w64(side == s);
-        if (leavers == 0) // (wave-uniform)
-            continue;
-        double *msg = s == 0 ? M.inner : M.outer;
-        const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(leavers >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)leavers, 0u));
-        unsigned base = 0;
-        if (side == s && below == 0) // the first leaver of the wavefront
-            base = atomicAdd(&M.cnt[s], (unsigned)__popcll(leavers));
-        base = __shfl(base, __ffsll((long long)leavers) - 1);
-        const unsigned place = base + below;
-        if (side == s && msg && place < (unsigned)M.capacity) {
-            particle_record_write(msg + 1 + (size_t)place * M.rec, n, A, X, M.rec);
-            A.alive[n] = 0;
-        }
+    if ((threadIdx.x & 63) == 0) {
+        wave_found[0][threadIdx.x >> 6] = found[0];
+        wave_found[1][threadIdx.x >> 6] = found[1];
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const unsigned *w = wave_found[threadIdx.x];
+        M.cnt[threadIdx.x * (PARTICLE_MIGRATE_GROUPS + 1) + blockIdx.x] = w[0] + w[1] + w[2] + w[3];
     }
 }
 
-// one lane, behind k_particles_emigrate: the clipped counts into word 0 of the messages, the totals, the counters back to 0
-__global__ void k_particles_emigrate_finish(const ParticleMigrate M)
+// one workgroup of 256 lanes, behind k_particles_emigrate_count: lane t sums its stretch of the M.groups counts, takes the
+// stretches below it from the LDS and writes the running sums back
+__global__ void __launch_bounds__(256) k_particles_emigrate_finish(const ParticleMigrate M)
 {
+    __shared__ unsigned stretch[256];
+    const int per = (M.groups + 255) / 256;
+    const int lo = min((int)threadIdx.x * per, M.groups), hi = min(lo + per, M.groups);
     for (int s = 0; s < 2; ++s) {
-        double *msg = s == 0 ? M.inner : M.outer;
-        const unsigned found = M.cnt[s];
-        const unsigned sent = !msg ? 0u : (found < (unsigned)M.capacity ? found : (unsigned)M.capacity);
-        if (msg)
-            msg[0] = (double)sent;
-        M.tot[s] += sent;
-        M.tot[3] += found - sent;
-        M.cnt[s] = 0;
+        unsigned *cnt = M.cnt + s * (PARTICLE_MIGRATE_GROUPS + 1);
+        unsigned sum = 0;
+        for (int k = lo; k < hi; ++k)
+            sum += cnt[k];
+        stretch[threadIdx.x] = sum;
+        __syncthreads();
+        unsigned run = 0;
+        for (unsigned k = 0; k < threadIdx.x; ++k)
+            run += stretch[k];
+        for (int k = lo; k < hi; ++k) {
+            const unsigned here = cnt[k];
+            cnt[k] = run;
+            run += here;
+        }
+        if (threadIdx.x == 255) { // (its stretch is the last one: `run` is the side's total)
+            cnt[M.groups] = run;
+            double *msg = s == 0 ? M.inner : M.outer;
+            const unsigned found = run;
+            const unsigned sent = !msg ? 0u : (found < (unsigned)M.capacity ? found : (unsigned)M.capacity);
+            if (msg)
+                msg[0] = (double)sent;
+            M.tot[s] += sent;
+            M.tot[3] += found - sent;
+        }
+        __syncthreads(); // `stretch` is written again for the other side
+    }
+}
+
+__global__ void __launch_bounds__(256) k_particles_emigrate(const ParticleArgs A, const ParticleAdaptive X, const ParticleMigrate M)
+{
+    __shared__ unsigned wave_found[2][4];
+    const unsigned *front[2] = {M.cnt, M.cnt + PARTICLE_MIGRATE_GROUPS + 1};
+    unsigned run[2] = {front[0][blockIdx.x], front[1][blockIdx.x]}; // leavers in front of this pass (workgroup-uniform)
+    if (run[0] == front[0][blockIdx.x + 1] && run[1] == front[1][blockIdx.x + 1])
+        return;
+    const int first = blockIdx.x * M.chunk, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < M.chunk; i += 256) {
+        const int n = first + i;
+        const int side = particle_leaves(A, M, n);
+        const unsigned long long leavers[2] = {__builtin_amdgcn_ballot_w64(side == 0), __builtin_amdgcn_ballot_w64(side == 1)};
+        if ((threadIdx.x & 63) == 0) {
+            wave_found[0][wave] = (unsigned)__popcll(leavers[0]);
+            wave_found[1][wave] = (unsigned)__popcll(leavers[1]);
+        }
+        __syncthreads();
+        unsigned waves_below[2] = {0u, 0u}, pass[2] = {0u, 0u};
+        for (int s = 0; s < 2; ++s)
+            for (int k = 0; k < 4; ++k) {
+                waves_below[s] += k < wave ? wave_found[s][k] : 0u;
+                pass[s] += wave_found[s][k];
+            }
+        if (side >= 0) {
+            double *msg = side == 0 ? M.inner : M.outer;
+            const unsigned long long mine = side == 0 ? leavers[0] : leavers[1];
+            const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(mine >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mine, 0u));
+            const unsigned place = (side == 0 ? run[0] + waves_below[0] : run[1] + waves_below[1]) + below;
+            if (msg && place < (unsigned)M.capacity) {
+                particle_record_write(msg + 1 + (size_t)place * M.rec, n, A, X, M.rec);
+                A.alive[n] = 0;
+            }
+        }
+        run[0] += pass[0];
+        run[1] += pass[1];
+        __syncthreads(); // wave_found is written again in the next pass
     }
 }
 

@@ -1,7 +1,7 @@
 // k_particles_step_explicit (PARTICLES_DEV false: dt and frame_angle are kernel arguments) and
 // k_particles_step_explicit_clock (true: they come from the device clock), see particles.h, which includes this file once
 // for each with PARTICLES_KERNEL, PARTICLES_DEV and PARTICLES_SLAB defined (k_particles_step_explicit_slab: one of several
-// slabs, see particle_rinf_id and particle_off_slab).
+// slabs, see particle_rinf_id and particle_off_slab; k_particles_step_explicit_slab_clock: that, reading the device clock).
 template <bool ADI, bool DRAG, bool CART>
 __global__ void __launch_bounds__(PARTICLES_EXPLICIT_BLOCK)
     PARTICLES_KERNEL(const Dev P, const ParticleArgs A, const ParticleAdaptive X)

@@ -119,6 +119,45 @@ class SlabSet:
             dts.append(self.step(snap))
         return dts
 
+    def run_steps_linked(self, nsteps: int, snap: bool = False, timeout: float = 300.0) -> List[int]:
+        """run_steps of every context, one thread each (the call blocks in the collectives until all slabs have made
+        them; ctypes releases the interpreter lock meanwhile).  The contexts share a host-link communicator
+        (comm_init_host on one path): without one on every slab, ValueError, and no slab is started.  With
+        particles_follow_run_steps and particles_slabs on every slab the particles are stepped and migrate inside the loop;
+        merged_particles() works unchanged afterwards.
+        -> the steps each slab took.  Every thread is waited for, until `timeout` seconds after the start, before anything
+        is raised: the first error of any slab, or TimeoutError if a slab has not returned by then.  A slab whose
+        neighbour failed leaves its collective with the link's own timeout (FCPT_HOSTLINK_TIMEOUT, 120 s unless set), so
+        keep `timeout` above that one: then no thread is still inside the library, on a context the caller may close, when
+        this raises."""
+        import threading
+        import time
+        links = {c.host_link for c in self.ctxs}
+        if len(links) != 1 or None in links:
+            raise ValueError("run_steps_linked: the contexts must share one host-link communicator (comm_init_host); "
+                             "theirs are %s" % sorted(map(str, links)))
+        done: List[Optional[int]] = [None] * len(self.ctxs)
+        errors: list = []
+
+        def run(k: int):
+            try:
+                done[k] = self.ctxs[k].run_steps(nsteps, snap=snap)
+            except BaseException as e:  # noqa: BLE001 -- handed to the caller below
+                errors.append((k, e))
+
+        threads = [threading.Thread(target=run, args=(k,), daemon=True) for k in range(len(self.ctxs))]
+        for t in threads:
+            t.start()
+        t_end = time.monotonic() + timeout
+        for t in threads:
+            t.join(max(0.0, t_end - time.monotonic()))
+        if errors:
+            raise errors[0][1]      # (the first that was raised: the others are usually its neighbours timing out)
+        stuck = [k for k, t in enumerate(threads) if t.is_alive()]
+        if stuck:
+            raise TimeoutError("run_steps_linked: slabs %s have not returned after %g s" % (stuck, timeout))
+        return [int(n) for n in done]
+
     def gather(self):
         """Global fields with overlap rings stripped (write2D, polargrid.cpp:135-180)."""
         out = {}

@@ -467,7 +467,7 @@ int fcpt_recalculate_derived(fcpt_ctx *ctx);
  * ParticleIntegrator: explicit (integrate_explicit_adaptive, :1677-2014) with its CartesianParticles state is selected
  * with fcpt_particles_integrator, below; the host driver does not offer it yet and still refuses the key.
  * Not covered (the host driver refuses setups that ask for them): disk gravity on particles, leapfrog, particles on
- * several slabs inside fcpt_run_steps or in the host driver. */
+ * several slabs in the host driver (the library runs them, inside fcpt_run_steps too: fcpt_particles_slabs, below). */
 typedef struct fcpt_particle_params {
     double particle_density;  /* ParticleDensity (code units) */
     double molecule_mass;     /* mu * m_u (code units), calc_tstop's m0 (particles.cpp:1139) */
@@ -591,8 +591,9 @@ int fcpt_particles_adaptive_set(fcpt_ctx *ctx, int64_t n, const double *timestep
 int fcpt_particles_adaptive_get(fcpt_ctx *ctx, int64_t capacity, double *timestep, double *facold, double *r_ddot,
                                 double *phi_ddot, uint32_t *accepted, uint32_t *rejected, int64_t *n);
 
-/* Particles inside fcpt_run_steps.  on = 1: every iteration of fcpt_run_steps on a single slab also takes the particle
- * step, where the reference has it (src/simulation.cpp:177-180): after the step length of the iteration is in force and
+/* Particles inside fcpt_run_steps.  on = 1: every iteration of fcpt_run_steps also takes the particle step (on one of
+ * several slabs: and the migration, see "Inside fcpt_run_steps" under fcpt_particles_slabs, below), where the reference
+ * has it (src/simulation.cpp:177-180): after the step length of the iteration is in force and
  * before the gas step, so it reads the gas of the start of the hydro step.  It is the step fcpt_particles_step would
  * take with dt = the step length the gas step uses, (indirect_x, indirect_y) and the bodies of the last fcpt_set_bodies
  * and frame_angle = OmegaFrame dt (one rounded product), with the integrator, cartesian, gas_drag and diffusion settings
@@ -602,12 +603,14 @@ int fcpt_particles_adaptive_get(fcpt_ctx *ctx, int64_t capacity, double *timeste
  * gives way to the policy launch while particles are present; the gas bits are the same).  A captured graph is replayed
  * only while the particle launch it holds is the one the context would queue now: whatever fcpt_particles_set,
  * _diffusion, _integrator, _adaptive_set, _timestep_init, fcpt_set_bodies or this call change in it leads to a new
- * capture, never to a stale replay (a setting put back before the next fcpt_run_steps changes nothing).  When fcpt_run_steps returns, fcpt_particles_diffusion_get().step has advanced by *nsteps_done, also
- * when there are no particles.  Guards 1 .. 10 go to the status word and are reported once by the next blocking
- * particle call, as after fcpt_particles_step.  Bodies do not move inside fcpt_run_steps.
+ * capture, never to a stale replay (a setting put back before the next fcpt_run_steps changes nothing).  When
+ * fcpt_run_steps returns, fcpt_particles_diffusion_get().step has advanced by *nsteps_done, also when there are no
+ * particles.  Guards 1 .. 10 go to the status word and are reported once by the next blocking particle call, as after
+ * fcpt_particles_step.  Bodies do not move inside fcpt_run_steps.
  * fcpt_run_steps returns FCPT_EINVAL, with *nsteps_done = 0, the clock untouched and nothing queued, while this is on and
  * the descriptor selects Integrator: Leapfrog, or the explicit integrator is selected and has no step sizes since the
- * last fcpt_particles_set.
+ * last fcpt_particles_set, or the context is one of several slabs and lacks a communicator or fcpt_particles_slabs
+ * {on = 1} (the message names which).
  * The setting belongs to the context and outlives fcpt_particles_set.  The default is 0: a context that never switches it
  * on allocates, launches and computes what it did before. */
 int fcpt_particles_follow_run_steps(fcpt_ctx *ctx, int32_t on);
@@ -628,12 +631,15 @@ int fcpt_particles_follow_run_steps_get(const fcpt_ctx *ctx, int32_t *on);
  * set by the receiver.  A record is the slot index followed by r, phi, r_dot, phi_dot, stokes and, once the explicit
  * integrator's step sizes exist (they must then exist on every slab), timestep, facold, r_ddot, phi_ddot: R = 6 or 10
  * doubles; id and radius are replicated and do not travel, the substep counters of fcpt_particles_adaptive_get stay with
- * the slab that took the step.  A migration message is always exactly fcpt_exchange_count doubles long: word 0 holds the
- * record count (as a double), the records follow, the rest is unspecified -- so the communicator of the ghost rings
- * carries it unchanged.  migrate_capacity records per side and call; 0 selects the built-in (fcpt_exchange_count - 1) / R,
- * a larger value is FCPT_EINVAL (when given, and again when the records grow to 10 doubles: the capacity in force is
- * the smaller).  A particle beyond the capacity stays with its owner, alive, and is counted in `deferred`: the overlap
- * rings still hold its gas, and the next call takes it.
+ * the slab that took the step.  A migration message of the calls below is always exactly fcpt_exchange_count doubles
+ * long (inside fcpt_run_steps it is cut to what the capacity can fill, see there): word 0 holds the record count (as a
+ * double), the records follow, the rest is unspecified -- so the communicator of the ghost rings carries it unchanged.
+ * migrate_capacity records per side and call; 0 selects the built-in (fcpt_exchange_count - 1) / R, a larger value is
+ * FCPT_EINVAL (when given, and again when the records grow to 10 doubles: the capacity in force is the smaller).  The
+ * leavers of a side are served in ascending slot order, and the records stand in the message in that order.  A particle
+ * beyond the capacity stays with its owner, alive, and is counted in `deferred`: the overlap rings still hold its gas,
+ * and the next call takes it.  Who goes and who waits depends on the particles alone, so two runs of one state agree
+ * in every message, counter and bit.
  *   fcpt_particles_migrate_pack / _unpack / _count mirror fcpt_exchange_pack / _unpack / _count (host or device buffers
  *   of _count doubles, NULL skips a side): slabs of one process hand the messages over themselves.  _unpack reads the
  *   count on the device and scatters by slot index; a record whose slot index is not in 0 .. n-1, or a count beyond the
@@ -653,9 +659,23 @@ int fcpt_particles_follow_run_steps_get(const fcpt_ctx *ctx, int32_t *on);
  * the particle is written and the id and the guard come back at the next blocking call.  The clamps at the grid's own
  * inner and outer edge are unchanged.
  *
- * fcpt_run_steps with fcpt_particles_follow_run_steps on returns FCPT_EINVAL on a context that is one of several slabs
- * (*nsteps_done = 0, the clock untouched, nothing queued): particles inside the multi-slab device loop are not covered,
- * nor does the host driver run particles with --ranks.
+ * Inside fcpt_run_steps (fcpt_particles_follow_run_steps on, nranks > 1).  The context needs a communicator
+ * (fcpt_comm_init or fcpt_comm_init_host) and on = 1; without either fcpt_run_steps returns FCPT_EINVAL before anything
+ * is queued (*nsteps_done = 0, the clock untouched), and the message of the multi-slab refusal names what is missing.
+ * Every slab's host calls fcpt_run_steps with the same arguments.  The order of an iteration:
+ *   snap = 0 (dt never leaves the device): CFL reduction and MIN all-reduce, time-step policy kernel, particle step (the
+ *     slab kernels in their clock-reading form: dt, OmegaFrame dt and the Philox counter come from device memory),
+ *     migration (pack, neighbour exchange on the context's stream, unpack), gas step, ghost exchange, post;
+ *   snap != 0: all-reduced CFL value to the host, fcpt_calculate_timestep, fcpt_snap_to_monitor, fcpt_particles_step(dt,
+ *     the indirect term of the last fcpt_set_bodies, OmegaFrame dt), fcpt_particles_migrate, fcpt_step, fcpt_exchange,
+ *     fcpt_post.
+ * Both give the bits of the same sequence called from the host.  The collective is issued in every iteration while follow
+ * and on are set, also on a context without particles (empty messages, no particle kernel), so that every slab makes the
+ * same calls.  With snap = 0 a migration message carries 1 + C R doubles, C the capacity in force (equal on all slabs, like
+ * R): a small migrate_capacity moves a small message every step.  fcpt_particles_migrate and _pack / _unpack / _count
+ * keep the full length.  The four totals below and fcpt_particles_diffusion_get().step keep running; guards 1 .. 12 are
+ * reported by the next blocking particle call.  No hipGraph is captured for a context with a communicator.
+ * The host driver does not run particles with --ranks.
  * sent_inner, sent_outer, received, deferred are running totals since fcpt_create, read-only (fcpt_particles_slabs
  * ignores them); fcpt_particles_slabs_get blocks.  The setting belongs to the context and outlives fcpt_particles_set;
  * switch it before fcpt_particles_set. */
@@ -808,8 +828,9 @@ int fcpt_post(fcpt_ctx *ctx, double dt);
  * calls it once more before the loop, src/simulation.cpp:463.) */
 int fcpt_apply_boundary(fcpt_ctx *ctx, double dt, int32_t final);
 
-/* K iterations of {cfl [+ MIN over the slabs], calculate_timestep, [snap], step, [exchange], post} without
- * returning to the caller, as sim::run does (src/simulation.cpp:515-553).  A context with a communicator
+/* K iterations of {cfl [+ MIN over the slabs], calculate_timestep, [snap], [particle step, [migration]], step,
+ * [exchange], post} without returning to the caller, as sim::run does (src/simulation.cpp:515-553); the particle step
+ * and, on several slabs, the migration with fcpt_particles_follow_run_steps.  A context with a communicator
  * (fcpt_comm_init) runs the multi-slab loop: every slab's host calls this with the same arguments.  If `snap` is non-zero the
  * step is snapped to monitor times and n_monitor advances.  nsteps_done may be
  * NULL.  Stops early when time reaches t_final = nsnapshots*nmonitor*monitor_timestep
