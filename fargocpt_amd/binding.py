@@ -415,6 +415,11 @@ class Context:
             self._call("transport_chunks", out.ctypes.data_as(C.POINTER(_i32)), _i32(n.value), C.byref(n))
         return out
 
+    def set_source_chunks(self, lengths):
+        """Explicit chunk lengths (>= 3 rings) of the marching source kernel from row 0 upward (empty: the built-in choice)."""
+        a = np.ascontiguousarray(lengths, dtype=np.int32)
+        self._call("set_source_chunks", a.ctypes.data_as(C.POINTER(_i32)), _i32(a.size))
+
     def source_chunks(self) -> np.ndarray:
         """(segment, first ring, one past the last) of every wavefront of the marching source kernel, dispatch order; empty: equal chunks."""
         n = _i32()

@@ -130,7 +130,11 @@ void apply_options(fcpt_ctx *c, bool at_create = true)
     c->P.sm_sched_n = 0;
     c->sm_sched_host.clear();
     if (c->sm_sched_dev && c->fused_source && c->march_source) {
-        const std::vector<int> sched = source_schedule(c->P, device_cus());
+        // (an explicit list, fcpt_set_source_chunks, stands in for the built-in table whatever source_graded says;
+        //  source_rows > 0 selects equal chunks over either)
+        const std::vector<int> sched = c->sm_lengths.empty() ? source_schedule(c->P, device_cus())
+                                       : o.source_rows > 0   ? std::vector<int>()
+                                                             : source_schedule_explicit(c->P, c->sm_lengths, nullptr);
         if (!sched.empty() && sched.size() <= c->sm_sched_cap &&
             hipMemcpy(c->sm_sched_dev, sched.data(), sched.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess) {
             c->P.sm_sched = c->sm_sched_dev;
@@ -494,6 +498,36 @@ int fcpt_transport_chunks(const fcpt_ctx *c, int32_t *tile_first_last, int32_t c
     for (int k = 0; k < n && k < capacity; ++k)
         for (int q = 0; q < 3; ++q)
             tile_first_last[3 * k + q] = c->tf_sched_host[4 * k + q];
+    return FCPT_OK;
+}
+
+int fcpt_set_source_chunks(fcpt_ctx *c, const int32_t *lengths, int32_t n)
+{
+    if (!c || n < 0 || (n > 0 && !lengths))
+        return FCPT_EINVAL;
+    if (c->stepped) {
+        set_error("fcpt_set_source_chunks between fcpt_step and fcpt_post");
+        return FCPT_EINVAL;
+    }
+    const std::vector<int> list(lengths, lengths + n);
+    bool refused = false;
+    const std::vector<int> table = source_schedule_explicit(c->P, list, &refused);
+    if (refused) { // the launcher folds the boundary call into the edge chunks of a table: three rows each at least
+        int k = 0;
+        while (k + 1 < n && list[k] >= 3)
+            ++k;
+        set_error("fcpt_set_source_chunks: chunk %d has %d rings, fewer than 3", k, list[k]);
+        return FCPT_EINVAL;
+    }
+    if (table.size() > c->sm_sched_cap) {
+        set_error("fcpt_set_source_chunks: %d wavefronts, the table holds %d", (int)(table.size() / 4), (int)(c->sm_sched_cap / 4));
+        return FCPT_EINVAL;
+    }
+    join_side(c);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->sm_lengths = list;
+    apply_options(c, false);
+    HIPCHK(hipGetLastError());
     return FCPT_OK;
 }
 

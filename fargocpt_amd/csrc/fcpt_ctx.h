@@ -84,6 +84,7 @@ struct fcpt_ctx {
     int *sm_sched_dev = nullptr;      // storage of Dev::sm_sched
     size_t sm_sched_cap = 0;          // ... in ints
     std::vector<int> sm_sched_host;
+    std::vector<int> sm_lengths;      // explicit chunk lengths from row 0 upward (fcpt_set_source_chunks); empty: built-in
     int *tf_sched_dev = nullptr;      // storage of Dev::tf_sched
     size_t tf_sched_cap = 0;          // ... in ints
     std::vector<int> tf_lengths;      // explicit chunk lengths in dispatch order (fcpt_set_transport_chunks; FCPT_TF_SCHEDULE at fcpt_create); empty: built-in

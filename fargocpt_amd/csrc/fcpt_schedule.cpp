@@ -162,6 +162,43 @@ std::vector<int> source_schedule(const Dev &P, int n_cu)
     const double g = (P.opt.source_graded > 0 && P.opt.source_graded < 100 ? P.opt.source_graded : (P.adiabatic ? 35 : 20)) * 0.01;
     return rank_matched_chunks(segs, rows, occ, wpr, cpc, 4, 3, g, nullptr);
 }
+// The same table from an explicit list of chunk lengths (fcpt_set_source_chunks: tuning runs and tests).  The rows
+// 0 .. nr of v_r are cut from row 0 upward into chunks of the given lengths, the last entry repeating; a remainder of
+// fewer than three rings is joined to the chunk before it (the launcher folds the boundary call into the edge chunks of
+// a table, which must have stored the three rows it reads themselves); the same cut serves every segment.  Entries in
+// dispatch order, chunk-major and the segments of a chunk side by side, padded with idle entries (first == last) to
+// whole workgroups of four wavefronts.  Empty where the marching kernels do not run (rings of fewer than 128 cells,
+// slabs of fewer than three rows) -- and, with *refused set, for a list that holds a length below three.
+std::vector<int> source_schedule_explicit(const Dev &P, const std::vector<int> &lengths, bool *refused)
+{
+    if (refused)
+        *refused = false;
+    for (int len : lengths)
+        if (len < 3) {
+            if (refused)
+                *refused = true;
+            return {};
+        }
+    const int rows = P.nr + 1; // v_r has rows 0 .. nr
+    if (lengths.empty() || P.nphi < 128 || rows < 3)
+        return {};
+    const int segs = segments_of(P.nphi);
+    std::vector<int> out;
+    int k0 = 0;
+    for (size_t c = 0; k0 < rows; ++c) {
+        const int len = lengths[c < lengths.size() ? c : lengths.size() - 1];
+        int k1 = len < rows - k0 ? k0 + len : rows;
+        if (rows - k1 < 3) // no crumbs
+            k1 = rows;
+        for (int s = 0; s < segs; ++s) {
+            const int e[4] = {s, k0, k1, 0};
+            out.insert(out.end(), e, e + 4);
+        }
+        k0 = k1;
+    }
+    out.resize((out.size() + 15) / 16 * 16, 0);
+    return out;
+}
 // Chunks of graded length for k_transport_fused, in dispatch order: (first ring, one past the last) pairs.
 //
 // Why: the wavefront trace of the kernel (profiles/tools/wave_trace_transport.py, profiles/r03_tf_wave_trace_uniform.txt) shows

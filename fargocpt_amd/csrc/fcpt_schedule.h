@@ -28,6 +28,7 @@ int march_len(const Dev &P, int n_cu, int rows_full);
 int source_rows(const Dev &P, int n_cu);
 int transport_rows(const Dev &P, int n_cu);
 std::vector<int> source_schedule(const Dev &P, int n_cu);
+std::vector<int> source_schedule_explicit(const Dev &P, const std::vector<int> &lengths, bool *refused);
 std::vector<int> transport_schedule(const Dev &P, int n_cu, const std::vector<int> &slow_rings, const std::vector<int> *lengths);
 bool transport_can_split(const Dev &P, int n_cu, bool shear_safe);
 bool source_march_applies(const Dev &P);

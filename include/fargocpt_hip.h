@@ -376,7 +376,16 @@ int fcpt_transport_chunks(const fcpt_ctx *ctx, int32_t *tile_first_last, int32_t
  * src/viscosity/): where one round of wavefronts covers the slab, every wavefront's chunk length is matched to the rate at
  * which its SIMD will serve it (option source_graded, per cent of difference between first and last rank; 0: equal
  * chunks).  Reports (segment of 59 cells, first ring, one past the last ring) per wavefront in the order of dispatch,
- * entries with first == last being idle; n_wavefronts = 0: equal chunks of source_rows rings. */
+ * entries with first == last being idle; n_wavefronts = 0: equal chunks of source_rows rings.
+ * fcpt_set_source_chunks replaces the table by one cut from an explicit list of chunk lengths -- a tuning and test hook,
+ * like the options: the rows 0 .. nr of v_r are cut from row 0 upward, the last entry repeating, a remainder of fewer than
+ * 3 rings joined to the chunk before it, the same cut for every segment; entries chunk by chunk, the segments of a chunk
+ * side by side, padded with idle entries to whole workgroups of 4 wavefronts (n = 0: back to the built-in choice).  The
+ * list stays in force across fcpt_set_option; source_rows > 0 selects equal chunks over it, source_graded does not matter
+ * to it.  FCPT_EINVAL for a length below 3 (a table's edge chunks apply the pre-transport boundary call, which reads three
+ * rows they must have stored themselves), for more wavefronts than the table holds (16 448), and between fcpt_step and
+ * fcpt_post.  The chunking never changes a result. */
+int fcpt_set_source_chunks(fcpt_ctx *ctx, const int32_t *lengths, int32_t n);
 int fcpt_source_chunks(const fcpt_ctx *ctx, int32_t *seg_first_last, int32_t capacity, int32_t *n_wavefronts);
 
 int fcpt_get_split(const fcpt_ctx *ctx, fcpt_split *out);

@@ -99,6 +99,10 @@ def draw(lib, seed):
     # of k_transport_fused, which the built-in choice only takes on grids far larger than these)
     if rng.integers(3) == 0:
         _EXTRA["transport_chunks"] = [int(v) for v in rng.integers(1, 1 + max(2, d.nr_global // 2), size=int(rng.integers(1, 7)))]
+    # appended draw: an explicit, ragged list of chunk lengths (3 rings at least) for the marching source kernels -- their
+    # table path, which the built-in choice only takes on grids far larger than these
+    if rng.integers(3) == 0:
+        _EXTRA["source_chunks"] = [int(v) for v in rng.integers(3, 1 + max(3, d.nr_global // 2), size=int(rng.integers(1, 7)))]
     return d, nslabs, planet
 
 
@@ -160,7 +164,7 @@ def test_random_configuration(product, oracle, seed):
     _judge("host_loop", seed, attempt)
 
 
-def _device_loop(lib, d, bodies, nsteps, noise=0.0):
+def _device_loop(lib, d, bodies, nsteps, noise=0.0, source_chunks=None):
     from fargocpt_amd import driver
     dd = d.copy()
     dd.rank, dd.nranks = 0, 1
@@ -171,6 +175,8 @@ def _device_loop(lib, d, bodies, nsteps, noise=0.0):
         rng = np.random.default_rng(7)
         fields = tuple(f * (1.0 + noise * rng.standard_normal(f.shape)) for f in fields)
     ctx = driver.make_context(lib, dd, fields=fields, radii=radii, bodies=bodies)
+    if source_chunks is not None and lib.has("set_source_chunks"):   # (the product's marching kernels; the oracle has no chunks)
+        ctx.set_source_chunks(source_chunks)
     S = driver.SlabSet([ctx])
     S.prepare()
     assert ctx.run_steps(nsteps) == nsteps
@@ -192,15 +198,16 @@ def test_random_configuration_device_loop(product, oracle, seed):
     def attempt(nsteps):
         nsteps = nsteps + 2
         try:
-            b = _device_loop(oracle, d, bodies, nsteps)
+            b = _device_loop(oracle, d, bodies, nsteps)   # (the oracle has no chunks: no list to hand on)
         except B.FcptError as err:
             assert "FCPT_EINVAL" in str(err)
             return None
         if not all(np.isfinite(v).all() for v in b.values()):
             pytest.skip("the oracle itself left the finite range: not a usable draw")
-        a = _device_loop(product, d, bodies, nsteps)
+        chunks = _EXTRA.get("source_chunks")
+        a = _device_loop(product, d, bodies, nsteps, source_chunks=chunks)
         if WIDE:
-            a2 = _device_loop(product, d, bodies, nsteps)
+            a2 = _device_loop(product, d, bodies, nsteps, source_chunks=chunks)
             assert a2["time"] == a["time"] and all(np.array_equal(a2[k], a[k], equal_nan=True) for k in fields), f"seed {seed}: run-to-run difference"
         errs = {k: rel_err(a[k], b[k]) for k in fields}
         terr = abs(a["time"] - b["time"]) / abs(b["time"])

@@ -149,7 +149,7 @@ def check_cells(outs, fields, tol):
 
 
 def run_pair(lib_a, lib_b, d, nsteps, bodies=None, amp=1e-3, snap=False, nslabs=(1, 1), dt_scale=1.0, noise=0.0,
-             irradiation=None, transport_chunks=None):
+             irradiation=None, transport_chunks=None, source_chunks=None):
     """Advance the same initial state `nsteps` with two libraries; returns the two global
     states and the two dt histories (a Runs list: with .desc and .radii of the global grid)."""
     outs = Runs()
@@ -179,6 +179,8 @@ def run_pair(lib_a, lib_b, d, nsteps, bodies=None, amp=1e-3, snap=False, nslabs=
             ctxs.append(driver.make_context(L, dd, fields=sub, radii=radii, bodies=bodies, irradiation=irradiation))
             if transport_chunks is not None and L.has("set_transport_chunks"):   # (the product's marching kernel; the oracle has no chunks)
                 ctxs[-1].set_transport_chunks(transport_chunks)
+            if source_chunks is not None and L.has("set_source_chunks"):   # (likewise the marching source kernels: the same list for every slab)
+                ctxs[-1].set_source_chunks(source_chunks)
         S = driver.SlabSet(ctxs)
         S.dt_scale = dt_scale
         S.prepare()
