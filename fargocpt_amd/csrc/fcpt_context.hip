@@ -20,9 +20,9 @@ void drop_graph(fcpt_ctx *c)
 // the caller's stream waits for the interior transport forked by fcpt_step_device_begin
 void join_side(fcpt_ctx *c)
 {
-    if (c->join_pending) {
+    if (c->ls.join_pending) {
         (void)hipStreamWaitEvent(c->stream, c->e_join, 0);
-        c->join_pending = false;
+        c->ls.join_pending = false;
     }
 }
 
@@ -107,29 +107,29 @@ int dev_upload(fcpt_ctx *c, const double **dst, const std::vector<double> &src)
 void apply_options(fcpt_ctx *c, bool at_create = true)
 {
     const Options &o = c->P.opt;
-    c->fused_source = o.fused_source != 0;
-    c->march_source = o.march_source != 0;
+    c->ls.fused_source = o.fused_source != 0;
+    c->ls.march_source = o.march_source != 0;
     {
         // StabilizeViscosity is implemented by the marching kernels and by the per-loop kernels, not by the three
         // intermediate fused ones: where the march does not run (narrow rings, switched off) fall back to the loops
-        const bool march_runs = c->fused_source && c->march_source && c->P.nphi >= 128 &&
+        const bool march_runs = c->ls.fused_source && c->ls.march_source && c->P.nphi >= 128 &&
                                 (!c->P.adiabatic || o.march_source_adi != 0);
         if ((c->P.stabilize || c->P.accel_force) && !march_runs) // (likewise BodyForceFromPotential: no)
-            c->fused_source = c->march_source = false;
+            c->ls.fused_source = c->ls.march_source = false;
     }
     const bool adi_march =
-        c->P.adiabatic && c->fused_source && c->march_source && c->P.nphi >= 128 && o.march_source_adi != 0;
+        c->P.adiabatic && c->ls.fused_source && c->ls.march_source && c->P.nphi >= 128 && o.march_source_adi != 0;
     c->P.lazy_derived = adi_march ? 1 : 0;
     c->P.inline_potential = (adi_march && !c->P.leapfrog && o.inline_potential != 0 && !c->P.accel_force) ? 1 : 0;
     c->P.damp_in_step = (c->damp_foldable && o.fused_damping != 0) ? 1 : 0;
-    c->cfl_interior = false;
-    c->potential_valid = false;
-    c->pressure_valid = false;
+    c->ls.cfl_interior = false;
+    c->ls.potential_valid = false;
+    c->ls.pressure_valid = false;
     // the wavefront table of the marching source kernels (the caller has synchronised the stream, or nothing has run yet)
     c->P.sm_sched = nullptr;
     c->P.sm_sched_n = 0;
     c->sm_sched_host.clear();
-    if (c->sm_sched_dev && c->fused_source && c->march_source) {
+    if (c->sm_sched_dev && c->ls.fused_source && c->ls.march_source) {
         // (an explicit list, fcpt_set_source_chunks, stands in for the built-in table whatever source_graded says;
         //  source_rows > 0 selects equal chunks over either)
         const std::vector<int> sched = c->sm_lengths.empty() ? source_schedule(c->P, device_cus())
@@ -158,10 +158,8 @@ void apply_options(fcpt_ctx *c, bool at_create = true)
             c->tf_sched_host = sched;
         }
     }
-    if (!at_create && c->P.adiabatic && !c->P.lazy_derived) {
-        launch_derived(c->P, c->stream); // the kernels that read c_s, H, nu, T from the grids expect them current
-        c->pressure_valid = true;
-    }
+    if (!at_create)
+        refresh_derived(c); // the kernels that read c_s, H, nu, T from the grids expect them current
 }
 
 int copy_initial_values(fcpt_ctx *c)
@@ -379,6 +377,8 @@ int fcpt_create(const fcpt_desc *d, const double *radii, fcpt_ctx **out)
     if (!c)
         return FCPT_ENOMEM;
     std::memset(&c->P, 0, sizeof(c->P)); // (padding too: the hipGraph replay compares Dev views with memcmp)
+    std::memset(&c->ls, 0, sizeof(c->ls)); // (likewise)
+    c->ls.ghosts_unknown = true;
     c->d = *d;
     if (d->eos != FCPT_EOS_IDEAL) // no energy equation: SubStep3 and with it every cooling term is not called
         c->d.cooling_surface = c->d.cooling_beta = 0; // (simulation.cpp:205-207 `if (parameters::Adiabatic)`)
@@ -420,7 +420,7 @@ int fcpt_set_option(fcpt_ctx *c, const char *name, int32_t value)
     }
     if (*slot == value)
         return FCPT_OK;
-    if (c->stepped) {
+    if (c->ls.stepped) {
         set_error("fcpt_set_option between fcpt_step and fcpt_post");
         return FCPT_EINVAL;
     }
@@ -472,7 +472,7 @@ int fcpt_set_transport_chunks(fcpt_ctx *c, const int32_t *lengths, int32_t n)
 {
     if (!c || n < 0 || (n > 0 && !lengths))
         return FCPT_EINVAL;
-    if (c->stepped) {
+    if (c->ls.stepped) {
         set_error("fcpt_set_transport_chunks between fcpt_step and fcpt_post");
         return FCPT_EINVAL;
     }
@@ -505,7 +505,7 @@ int fcpt_set_source_chunks(fcpt_ctx *c, const int32_t *lengths, int32_t n)
 {
     if (!c || n < 0 || (n > 0 && !lengths))
         return FCPT_EINVAL;
-    if (c->stepped) {
+    if (c->ls.stepped) {
         set_error("fcpt_set_source_chunks between fcpt_step and fcpt_post");
         return FCPT_EINVAL;
     }
@@ -678,17 +678,17 @@ int fcpt_upload(fcpt_ctx *c, int32_t f, const double *host)
         // a replaced state grid: nothing derived from the old one may be reused.  The non-lazy ideal-EOS paths read
         // c_s, H, nu, T from grids that only fcpt_init_physics / fcpt_recalculate_derived / fcpt_post refresh --
         // that contract (restart_load, restart.cpp:18-139) stays; what the library evaluates lazily is redone.
-        c->pressure_valid = false;
-        c->potential_valid = false;
-        c->stepped = false;
-        c->ghosts_unknown = true;
+        c->ls.pressure_valid = false;
+        c->ls.potential_valid = false;
+        c->ls.stepped = false;
+        c->ls.ghosts_unknown = true;
         drop_graph(c); // its launches were chosen for ghost rings that satisfied the boundary conditions
     }
     if (f == FCPT_F_QPLUS || f == FCPT_F_QMINUS)
-        c->qdiff_valid = false;
+        c->ls.qdiff_valid = false;
     if (f == FCPT_F_SCALE_HEIGHT)
-        c->potential_valid = false;
-    c->cfl_interior = false;
+        c->ls.potential_valid = false;
+    c->ls.cfl_interior = false;
     return FCPT_OK;
 }
 
@@ -702,12 +702,12 @@ int fcpt_download(fcpt_ctx *c, int32_t f, double *host)
     if (f == FCPT_F_PRESSURE || (c->P.adiabatic && (f == FCPT_F_SOUNDSPEED || f == FCPT_F_SCALE_HEIGHT ||
                                                      f == FCPT_F_VISCOSITY || f == FCPT_F_TEMPERATURE)))
         ensure_pressure(c);
-    if (f == FCPT_F_POTENTIAL && (!c->potential_valid || c->P.accel_force)) {
+    if (f == FCPT_F_POTENTIAL && (!c->ls.potential_valid || c->P.accel_force)) {
         // evaluated inside the source march (ideal EOS), or not at all (BodyForceFromPotential: no): the grid on
         // request, from the current state and bodies
         launch_potential(c->P, c->stream);
         if (!c->P.accel_force) // (there the flag speaks for the acceleration grids)
-            c->potential_valid = !c->P.adiabatic;
+            c->ls.potential_valid = !c->P.adiabatic;
     }
     HIPCHK(hipMemcpyAsync(host, c->grid[f], grid_count(c, f) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -741,8 +741,8 @@ int fcpt_set_bodies(fcpt_ctx *c, int32_t n, const double *x, const double *y, co
     }
     P.indirect_x = ix;
     P.indirect_y = iy;
-    c->potential_valid = false;
-    c->has_mid = false;
+    c->ls.potential_valid = false;
+    c->ls.has_mid = false;
     return FCPT_OK;
 }
 
@@ -759,7 +759,7 @@ int fcpt_set_bodies_midstep(fcpt_ctx *c, int32_t n, const double *x, const doubl
         c->mm[k] = m[k];
         c->mrsm[k] = rsm ? rsm[k] : 0.0;
     }
-    c->has_mid = true;
+    c->ls.has_mid = true;
     return FCPT_OK;
 }
 
@@ -894,8 +894,8 @@ int fcpt_init_physics(fcpt_ctx *c)
     apply_boundary(c, false);
     if (int rc = copy_initial_values(c))
         return rc;
-    c->potential_valid = false;
-    c->pressure_valid = true;
+    c->ls.potential_valid = false;
+    c->ls.pressure_valid = true;
     HIPCHK(hipGetLastError());
     return FCPT_OK;
 }
@@ -908,15 +908,10 @@ int fcpt_recalculate_derived(fcpt_ctx *c)
         return FCPT_EINVAL;
     join_side(c);
     ProfScope prof_scope(c);
-    c->stepped = false;
-    c->cfl_interior = false;
-    c->potential_valid = false;
-    if (c->P.adiabatic && !c->P.lazy_derived) {
-        launch_derived(c->P, c->stream);
-        c->pressure_valid = true;
-    } else {
-        c->pressure_valid = false; // evaluated lazily
-    }
+    c->ls.stepped = false;
+    c->ls.cfl_interior = false;
+    c->ls.potential_valid = false;
+    refresh_derived(c);
     HIPCHK(hipGetLastError());
     return FCPT_OK;
 }

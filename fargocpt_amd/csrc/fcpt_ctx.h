@@ -1,7 +1,8 @@
 // Shared by the translation units of the device side of the C ABI: the context structure and the helpers that more
 // than one of them uses.  fcpt_context.hip: creation (the device stages: uploads, grids, clock -- what it uploads is
 // built by the host unit fcpt_tables.cpp, declared in fcpt_internal.h), options, transfers, initial physics, profiling;
-// fcpt_step.hip: CFL, the step, the final boundary call, the run loop (+ hipGraph replay);
+// fcpt_step.hip: CFL, the step, the final boundary call, the run loop (+ hipGraph replay) -- it enqueues what the host
+// unit fcpt_plan.cpp decides (fcpt_plan.h) from the Dev view and the LaunchState below;
 // fcpt_exchange.hip: ghost exchange and the RCCL entry points; fcpt_particles.hip: dust particles.
 #ifndef FCPT_CTX_H
 #define FCPT_CTX_H
@@ -40,46 +41,52 @@ struct ParticleLaunch {
     ParticleAdaptive X;
 };
 
+// The host-side state that decides launches and outlives a call of the ABI, beside the Dev view: what is current on the
+// device, what is still owed to it.  One plain struct, zero-filled at fcpt_create the way Dev is: the hipGraph replay
+// compares it as a whole and the rollback of a failed capture assigns it as a whole.  What one function of an
+// iteration tells the next (StepPlan, KickResult, PendingGated) is passed by value and never stored here.
+struct LaunchState {
+    bool potential_valid; // the potential grid holds the potential of the current bodies (and scale height)
+    bool pressure_valid;  // the pressure grid (ideal EOS: every derived grid) is that of the current state
+    bool stepped;         // fcpt_step ran since the last fcpt_post
+    bool cfl_interior;    // fcpt_cfl_begin evaluated the interior rings of the current state
+    bool ghosts_unknown;  // a state grid was uploaded since the last boundary call
+    bool qdiff_valid;     // Dev::qdiff holds Q+ - Q- of the grids (written by the last kick's march)
+    // fcpt_run_steps (single slab): the final boundary call of the step just taken has not been launched yet -- the next
+    // iteration's CFL launch carries it (k_cfl_rings_bc), or flush_deferred_boundary() does.  Never set when the function returns.
+    bool bc_deferred;
+    bool has_mid;         // leapfrog: fcpt_set_bodies_midstep gave the bodies at the mid-step time
+    bool join_pending;    // fcpt_step_device_begin forked the interior transport to `side`: join_side() is owed
+    bool fused_source, march_source; // the options of these names after apply_options() (StabilizeViscosity may clear them)
+};
+
+// the gated azimuthal launch of the fallback transport that enqueue_step left to the final boundary call of the step
+// (fcpt_run_steps on one slab, StepPlan::gated_with_boundary): from enqueue_step to enqueue_post, inside one iteration
+struct PendingGated {
+    bool pending = false;
+    GatedTheta launch;
+};
+
 struct fcpt_ctx {
     fcpt_desc d;
     fcpt_split s;
     HostGeometry geo;
     std::vector<double> radii;
     Dev P;
+    LaunchState ls; // (zero-filled by fcpt_create)
     hipStream_t stream = nullptr;
     std::vector<void *> allocs;
     double *d_cs_ring = nullptr;
     double *grid[FCPT_F_COUNT] = {};
     DampRange damp[4][2]; // [vrad, vaz, sigma, energy][inner, outer]
-    bool potential_valid = false;
     DevClock *h_clk = nullptr; // pinned staging copy
     Profiler prof;
     bool profiling = false;
-    bool fused_source = true;
-    int src_parts = 0; // segments of ring sums left by the last k_source_march
-    bool kick_energy_b = false;
-    bool kick_bc_folded = false; // the last kick applied the boundary conditions that follow it
-    bool ghosts_unknown = true;  // a state grid was uploaded since the last boundary call
     // the dt of the next step is the CFL policy's (set by calculate_timestep*, consumed by the step):
     // with CFL <= 0.8 that keeps it inside the FARGO shear limit
     bool policy_dt_dev = false;
-    double policy_dt_host = -1.0; // the last kick left the energy in energy_b (marching source step, ideal EOS)
-    bool march_source = true;
-    bool stepped = false; // fcpt_step ran since the last fcpt_post
-    // fcpt_run_steps (single slab): the final boundary call of the step just taken has not been launched yet -- the next
-    // iteration's CFL launch carries it (k_cfl_rings_bc), or flush_deferred_boundary() does.  Never set when the function returns.
-    bool bc_deferred = false;
-    bool skip_q_store = false; // fcpt_run_steps: the step about to be queued is not the call's last (Dev::q_skip for its kick)
-    // fcpt_run_steps (single slab): the gated azimuthal launch of the fallback transport is queued together with the final
-    // boundary call of the step (one launch); never pending when a function of the ABI returns
-    bool want_gated_deferred = false, gated_pending = false;
-    GatedTheta gated;
-    // fcpt_run_steps (single slab): the CFL fold + time-step policy of the step about to be taken has not been launched --
-    // the marching source kernel queued next does it in its prologue (or enqueue_kick launches k_cfl_final first)
-    bool fold_pending = false;
-    bool cfl_interior = false; // fcpt_cfl_begin evaluated the interior rings of the current state
+    double policy_dt_host = -1.0;
     bool damp_any = false;     // this slab holds rings of a damping zone
-    bool qdiff_valid = false;       // Dev::qdiff holds Q+ - Q- of the grids (written by the last kick's march)
     std::vector<int> ring_ref_damped; // per ring: 1 if the folded damping loads reference values there (costlier rings of the transport)
     int *sm_sched_dev = nullptr;      // storage of Dev::sm_sched
     size_t sm_sched_cap = 0;          // ... in ints
@@ -94,15 +101,12 @@ struct fcpt_ctx {
     // marches the chunks with the neighbours' ghost rings, packs and sends them
     hipStream_t side = nullptr;
     hipEvent_t e_fork = nullptr, e_join = nullptr;
-    bool join_pending = false;
-    bool pressure_valid = false;
     // fcpt_disk_on_bodies_begin / _end: first-stage sums [body][block][4] followed by the 4 * FCPT_MAX_BODIES results
     // (allocated by the first call), their pinned host copy, the event behind the copy, the n of the pending call
     double *dob_part = nullptr, *dob_host = nullptr;
     hipEvent_t e_dob = nullptr;
     int dob_pending = 0;
-    // leapfrog: bodies at the mid-step time (simulation.cpp:359-366)
-    bool has_mid = false;
+    // leapfrog: bodies at the mid-step time (simulation.cpp:359-366; LaunchState::has_mid)
     double mx[FCPT_MAX_BODIES], my[FCPT_MAX_BODIES], mm[FCPT_MAX_BODIES], mrsm[FCPT_MAX_BODIES];
     // radial slabs over RCCL (fcpt_comm_init): communicator, packed ghost-ring buffers [send inner, send outer,
     // recv inner, recv outer], the device scalar of the MIN all-reduce, a stream for transfers that overlap the CFL
@@ -140,7 +144,7 @@ struct fcpt_ctx {
     unsigned long long *part_mtot = nullptr;
     // fcpt_run_steps on launch-bound grids: a captured hipGraph of `graph_cycle` consecutive steps (the out-of-place
     // transport swaps grid pointers, so the launch arguments repeat with period 2), replayed while the host-side state
-    // that decided the launches (the whole Dev view, the lazy-evaluation flags) is what it was at capture
+    // that decided the launches (the whole Dev view, the whole LaunchState) is what it was at capture
     hipGraphExec_t graph_exec = nullptr;
     hipGraph_t graph = nullptr;
     hipStream_t capture_stream = nullptr;
@@ -148,7 +152,7 @@ struct fcpt_ctx {
     long long graph_replays = 0; // hipGraphLaunch calls issued so far (read-only option "graph_replays")
     bool graph_failed = false;
     Dev graph_P;
-    unsigned graph_flags = 0;
+    LaunchState graph_ls;
     ParticleLaunch graph_part = {}; // ... and the particle launch inside the cycle
 };
 
@@ -204,8 +208,10 @@ void apply_boundary_view(fcpt_ctx *c, const Dev &P, bool final, bool damping_don
 void apply_boundary(fcpt_ctx *c, bool final);
 void ensure_pressure(fcpt_ctx *c);
 void enqueue_cfl(fcpt_ctx *c, int apply_policy);
-void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool split = false);
-void enqueue_post(fcpt_ctx *c, bool may_defer_boundary = false);
+void refresh_derived(fcpt_ctx *c);
+void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool split = false, const StepPlan &plan = StepPlan(),
+                  PendingGated *gated = nullptr);
+void enqueue_post(fcpt_ctx *c, bool may_defer_boundary = false, const PendingGated *gated = nullptr);
 void flush_deferred_boundary(fcpt_ctx *c);
 // fcpt_particles.hip
 void particles_free(fcpt_ctx *c);

@@ -7,6 +7,7 @@
 
 #include "fcpt_internal.h"
 #include "fcpt_schedule.h"
+#include "fcpt_plan.h"
 
 namespace fcpt {
 
@@ -100,14 +101,12 @@ void launch_particles_counter_offset(unsigned long long *offset, unsigned long l
 void launch_source_fused(const Dev &P, hipStream_t st);
 int launch_source_march(const Dev &P, hipStream_t st, bool fold_bc, bool *bc_folded, bool fold_cfl = false);
 void launch_cfl_final(const Dev &P, int apply_policy, hipStream_t st);
-bool cfl_by_rings(const Dev &P);
 void launch_viscous_fused(const Dev &P, hipStream_t st);
 void launch_derived(const Dev &P, hipStream_t st);
 void launch_pressure(const Dev &P, hipStream_t st);
 void launch_temperature(const Dev &P, hipStream_t st);
 void launch_cfl(const Dev &P, int apply_policy, hipStream_t st, bool interior_done = false);
 bool launch_cfl_interior(const Dev &P, hipStream_t st);
-bool cfl_bc_mergeable(const Dev &P);
 void launch_cfl_bc(const Dev &P, int apply_policy, hipStream_t st);
 void launch_clock_set_dt(DevClock *clk, double dt, hipStream_t st);
 void launch_clock_scale_dt(DevClock *clk, int mode, double dt, double factor, hipStream_t st);

@@ -28,14 +28,26 @@ void apply_boundary(fcpt_ctx *c, bool final) { apply_boundary_view(c, c->P, fina
 // isothermal pressure is Sigma c_s^2 with c_s fixed per ring: the marching source kernel forms
 // it in registers, so the grid is only materialised for callers that ask for it
 // (ideal EOS with the marching source step: the same holds for T, c_s, H and nu)
-void ensure_pressure(fcpt_ctx *c)
+static void ensure_pressure_view(fcpt_ctx *c, const Dev &P)
 {
-    if (!c->pressure_valid) {
-        if (c->P.adiabatic)
-            launch_derived(c->P, c->stream);
+    if (!c->ls.pressure_valid) {
+        if (P.adiabatic)
+            launch_derived(P, c->stream);
         else
-            launch_pressure(c->P, c->stream);
-        c->pressure_valid = true;
+            launch_pressure(P, c->stream);
+        c->ls.pressure_valid = true;
+    }
+}
+void ensure_pressure(fcpt_ctx *c) { ensure_pressure_view(c, c->P); }
+
+// recalculate_derived_disk_quantities: the derived grids now where kernels read them from the grids, else on request
+void refresh_derived(fcpt_ctx *c)
+{
+    if (c->P.adiabatic && !c->P.lazy_derived) {
+        launch_derived(c->P, c->stream);
+        c->ls.pressure_valid = true;
+    } else {
+        c->ls.pressure_valid = false; // P only (ideal EOS: c_s, H, nu, T too), evaluated lazily
     }
 }
 
@@ -43,45 +55,71 @@ void ensure_pressure(fcpt_ctx *c)
 
 namespace {
 
-// one gas "kick" (source terms, artificial viscosity, viscosity, SubStep3) with the step length
-// currently in the device clock.  Returns true if the result is in (vrad_b, vazi_b).
-bool enqueue_kick(fcpt_ctx *c, bool fold_bc = false)
+StepFacts step_facts(const fcpt_ctx *c)
 {
-    const Dev &P = c->P;
+    StepFacts F;
+    F.leapfrog = c->d.integrator == FCPT_INTEGRATOR_LEAPFROG;
+    F.damping_configured = c->d.damping != 0;
+    F.slab_damped = c->damp_any;
+    F.fused_source = c->ls.fused_source;
+    F.march_source = c->ls.march_source;
+    F.particles = c->part_follow && c->part.n > 0;
+    return F;
+}
+
+// the four state grids as the ABI hands them out: wherever the out-of-place transport (or a rollback) left Dev's pointers
+void sync_state_grids(fcpt_ctx *c)
+{
+    c->grid[FCPT_F_SIGMA] = c->P.sigma;
+    c->grid[FCPT_F_VRAD] = c->P.vrad;
+    c->grid[FCPT_F_VAZI] = c->P.vazi;
+    c->grid[FCPT_F_ENERGY] = c->P.energy;
+}
+
+struct KickResult {
+    bool vel_in_b;    // the velocities are in (vrad_b, vazi_b)
+    bool energy_in_b; // ... and the energy in energy_b (marching source step, ideal EOS)
+    int ring_parts;   // segments of ring sums of v_phi left by k_source_march (0: none)
+    bool bc_folded;   // the kick applied the boundary conditions that follow it
+};
+
+// one gas "kick" (source terms, artificial viscosity, viscosity, SubStep3) with the step length currently in the device
+// clock, launched with the view P.  fold_bc: and the boundary call that follows the first kick of a step;
+// plan.cfl_policy == 2: the CFL fold + time-step policy of this step has not been launched yet; plan.skip_q_store
+KickResult enqueue_kick(fcpt_ctx *c, const Dev &P, bool fold_bc, const StepPlan &plan)
+{
     hipStream_t st = c->stream;
-    c->kick_bc_folded = false;
-    if (c->fold_pending && !c->fused_source) {
-        launch_cfl_final(P, 1, st);
-        c->fold_pending = false;
-    }
-    if (c->fused_source) {
-        // one pass: (v[, e]) -> (v_b[, e_b]); fold_bc: and the boundary call that follows the first kick of a step
-        const bool fold_cfl = c->fold_pending && c->march_source && source_march_applies(P);
-        if (c->fold_pending && !fold_cfl)
+    KickResult r = {false, false, 0, false};
+    const bool fold_pending = plan.cfl_policy == 2;
+    if (c->ls.fused_source) {
+        // one pass: (v[, e]) -> (v_b[, e_b])
+        const bool fold_cfl = fold_pending && c->ls.march_source && source_march_applies(P);
+        if (fold_pending && !fold_cfl)
             launch_cfl_final(P, 1, st);
-        c->fold_pending = false;
         int segs = 0;
-        if (c->march_source && c->skip_q_store && P.adiabatic && cfl_by_rings(P)) {
+        if (c->ls.march_source && plan.skip_q_store && P.adiabatic && cfl_by_rings(P)) {
             Dev Q = P; // (Q+ and Q- themselves are read by nothing on the device in this configuration: the ring kernel of the CFL reduction takes their difference)
             Q.q_skip = 1;
-            segs = launch_source_march(Q, st, fold_bc, &c->kick_bc_folded, fold_cfl);
-        } else if (c->march_source) {
-            segs = launch_source_march(P, st, fold_bc, &c->kick_bc_folded, fold_cfl);
+            segs = launch_source_march(Q, st, fold_bc, &r.bc_folded, fold_cfl);
+        } else if (c->ls.march_source) {
+            segs = launch_source_march(P, st, fold_bc, &r.bc_folded, fold_cfl);
         }
-        c->skip_q_store = false;
-        c->src_parts = segs > 0 ? segs : 0;
-        c->kick_energy_b = segs != 0 && P.adiabatic;
-        c->qdiff_valid = segs != 0 && P.adiabatic; // the march wrote Q+ - Q- beside Q+ and Q-; the loop kernels do not
+        r.vel_in_b = true;
+        r.ring_parts = segs > 0 ? segs : 0;
+        r.energy_in_b = segs != 0 && P.adiabatic;
+        c->ls.qdiff_valid = segs != 0 && P.adiabatic; // the march wrote Q+ - Q- beside Q+ and Q-; the loop kernels do not
         if (!segs) {
-            ensure_pressure(c);
+            ensure_pressure_view(c, P);
             launch_source_fused(P, st);          // (v) -> (v_b) -> (v)
             launch_recalculate_viscosity(P, st);
             launch_viscous_fused(P, st);         // (v) -> (v_b); ideal EOS: + viscous heating + SubStep3
         }
-        return true;
+        return r;
     }
-    c->qdiff_valid = false;
-    ensure_pressure(c);
+    if (fold_pending)
+        launch_cfl_final(P, 1, st);
+    c->ls.qdiff_valid = false;
+    ensure_pressure_view(c, P);
     launch_source(P, st);
     launch_artificial_viscosity(P, st);
     launch_recalculate_viscosity(P, st);
@@ -89,61 +127,58 @@ bool enqueue_kick(fcpt_ctx *c, bool fold_bc = false)
     launch_viscous_update(P, st);
     if (P.adiabatic)
         launch_substep3(P, 1, st);
-    return false;
+    return r;
+}
+
+// the bodies at the mid-step time (fcpt_set_bodies_midstep) into a view
+void set_mid_bodies(const fcpt_ctx *c, Dev &M)
+{
+    for (int k = 0; k < M.nbodies; ++k) {
+        M.bx[k] = c->mx[k];
+        M.by[k] = c->my[k];
+        M.bm[k] = c->mm[k];
+        M.brsm[k] = c->mrsm[k];
+    }
 }
 
 void enqueue_potential(fcpt_ctx *c, bool midstep)
 {
     Dev &P = c->P;
-    if (midstep && P.adiabatic && P.lazy_derived) {
-        // the mid-step potential of step_LeapFrog sees the scale height of the first kick (left in the
-        // grid by k_source_march_adi), not one derived from the transported state
+    // the mid-step potential of step_LeapFrog sees the scale height of the first kick (left in the
+    // grid by k_source_march_adi), not one derived from the transported state
+    const bool kick_height = midstep && P.adiabatic && P.lazy_derived;
+    if (kick_height || (midstep && c->ls.has_mid)) {
         Dev M = P;
-        M.lazy_derived = 0;
-        if (c->has_mid)
-            for (int k = 0; k < P.nbodies; ++k) {
-                M.bx[k] = c->mx[k];
-                M.by[k] = c->my[k];
-                M.bm[k] = c->mm[k];
-                M.brsm[k] = c->mrsm[k];
-            }
+        if (kick_height)
+            M.lazy_derived = 0;
+        if (c->ls.has_mid)
+            set_mid_bodies(c, M);
         launch_body_force(M, c->stream);
-        c->potential_valid = false;
-        return;
-    }
-    if (midstep && c->has_mid) {
-        Dev M = P;
-        for (int k = 0; k < P.nbodies; ++k) {
-            M.bx[k] = c->mx[k];
-            M.by[k] = c->my[k];
-            M.bm[k] = c->mm[k];
-            M.brsm[k] = c->mrsm[k];
-        }
-        launch_body_force(M, c->stream);
-        c->potential_valid = false; // the grid now holds the mid-step potential
+        c->ls.potential_valid = false; // the grid now holds the mid-step potential
         return;
     }
     if (P.inline_potential) { // k_source_march_adi evaluates it ring by ring; the grid is only filled on request
-        c->potential_valid = false;
+        c->ls.potential_valid = false;
         return;
     }
-    if (P.adiabatic || !c->potential_valid) {
+    if (P.adiabatic || !c->ls.potential_valid) {
         launch_body_force(P, c->stream); // CalculateNbodyPotential | CalculateAccelOnGas; static when H and the bodies are
-        c->potential_valid = true;
+        c->ls.potential_valid = true;
     }
 }
-
-// the gas part of step_Euler up to Transport (simulation.cpp:167-217), or of step_LeapFrog
-// (simulation.cpp:316-393): kick 1/2 (dt/2), drift (dt), kick 2/2 (dt/2).  `dt_dev`: the step
 
 } // namespace
 
 namespace fcpt {
 
-void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool split)
+// the gas part of step_Euler up to Transport (simulation.cpp:167-217), or of step_LeapFrog
+// (simulation.cpp:316-393): kick 1/2 (dt/2), drift (dt), kick 2/2 (dt/2).  `dt_dev`: the step length is in the device
+// clock.  plan: what fcpt_run_steps asks of this step (an ABI call: the defaults); gated: where the transport may leave
+// the gated launch of its fallback (plan.gated_with_boundary)
+void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool split, const StepPlan &plan, PendingGated *gated)
 {
     join_side(c);
-    c->cfl_interior = false;
+    c->ls.cfl_interior = false;
     const Dev &P = c->P;
     hipStream_t st = c->stream;
     const bool frog = c->d.integrator == FCPT_INTEGRATOR_LEAPFROG;
@@ -156,21 +191,18 @@ void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool spl
     //  rewrites Sigma's ghost ring while neighbouring wavefronts may still read it -- harmless only when the values
     //  are the ones already there, so that one step takes the separate launch)
     //  likewise a second fcpt_step without fcpt_post in between: the ghost rings are the transport's, not a boundary call's)
-    const bool in_b = enqueue_kick(c, !c->ghosts_unknown && !c->stepped);
-    c->ghosts_unknown = false;
+    const KickResult k1 = enqueue_kick(c, P, !c->ls.ghosts_unknown && !c->ls.stepped, plan);
+    c->ls.ghosts_unknown = false;
     Dev Q = P; // view with the post-kick velocities
-    if (in_b) {
+    if (k1.vel_in_b) {
         Q.vrad = P.vrad_b;
         Q.vazi = P.vazi_b;
     }
-    if (c->kick_energy_b)
+    if (k1.energy_in_b)
         Q.energy = P.energy_b;
-    c->kick_energy_b = false;
-    Q.src_ring_nparts = in_b ? c->src_parts : 0; // ring sums of v_phi left by k_source_march
-    c->src_parts = 0;
-    if (!c->kick_bc_folded) // (else the source march applied it on its edge chunks)
+    Q.src_ring_nparts = k1.vel_in_b ? k1.ring_parts : 0; // ring sums of v_phi left by k_source_march
+    if (!k1.bc_folded) // (else the source march applied it on its edge chunks)
         apply_boundary_view(c, Q, false);
-    c->kick_bc_folded = false;
     if (frog)
         launch_clock_scale_dt(P.clk, 2, 0.0, 1.0, st); // dt <- step (saved in cfl_dt)
     launch_massflow(Q, st); // WriteMassFlow: what this Transport() carries through the interfaces
@@ -182,12 +214,13 @@ void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool spl
         (void)launch_transport(Q, P, c->side, TRANSPORT_INTERIOR);
         (void)hipEventRecord(c->e_join, c->side);
         tr = launch_transport(Q, P, st, TRANSPORT_EDGES);
-        c->join_pending = true;
+        c->ls.join_pending = true;
     } else {
-        tr = launch_transport(Q, P, st, TRANSPORT_ALL, c->want_gated_deferred && !frog ? &c->gated : nullptr);
-        c->gated_pending = tr.gated_pending != 0;
+        const bool leave_gated = gated && plan.gated_with_boundary && !frog;
+        tr = launch_transport(Q, P, st, TRANSPORT_ALL, leave_gated ? &gated->launch : nullptr);
+        if (gated)
+            gated->pending = tr.gated_pending != 0;
     }
-    c->want_gated_deferred = false;
     if (!tr.marched)
         launch_clock_advance(P.clk, st);
     // the marching transport is out of place: the new state may sit in the scratch twins
@@ -199,88 +232,63 @@ void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool spl
         std::swap(c->P.vrad, c->P.vrad_b);
     if (tr.vazi != c->P.vazi)
         std::swap(c->P.vazi, c->P.vazi_b);
-    c->grid[FCPT_F_SIGMA] = c->P.sigma;
-    c->grid[FCPT_F_VRAD] = c->P.vrad;
-    c->grid[FCPT_F_VAZI] = c->P.vazi;
-    c->grid[FCPT_F_ENERGY] = c->P.energy;
+    sync_state_grids(c);
     if (frog) {
         launch_clock_scale_dt(P.clk, 2, 0.0, 0.5, st); // dt <- step/2
         enqueue_potential(c, true);
-        c->pressure_valid = false; // compute_pressure(data), simulation.cpp:378
+        c->ls.pressure_valid = false; // compute_pressure(data), simulation.cpp:378
         if (P.adiabatic && !P.lazy_derived)
             ensure_pressure(c);
-        c->P.kick_time_shift = 1; // SubStep3 of the second kick runs at midstep_time (simulation.cpp:388)
-        const bool home = enqueue_kick(c);
-        c->P.kick_time_shift = 0;
-        if (home) { // result in the *_b buffers: bring it home
+        Dev K = P;
+        K.kick_time_shift = 1; // SubStep3 of the second kick runs at midstep_time (simulation.cpp:388)
+        const KickResult k2 = enqueue_kick(c, K, false, StepPlan());
+        if (k2.vel_in_b) { // result in the *_b buffers: bring it home
             const size_t ns = (size_t)P.nr * P.nphi * sizeof(double), nv = (size_t)(P.nr + 1) * P.nphi * sizeof(double);
             (void)hipMemcpyAsync(P.vrad, P.vrad_b, nv, hipMemcpyDeviceToDevice, st);
             (void)hipMemcpyAsync(P.vazi, P.vazi_b, ns, hipMemcpyDeviceToDevice, st);
-            if (c->kick_energy_b)
+            if (k2.energy_in_b)
                 (void)hipMemcpyAsync(P.energy, P.energy_b, ns, hipMemcpyDeviceToDevice, st);
-            c->kick_energy_b = false;
         }
         launch_clock_scale_dt(P.clk, 2, 0.0, 1.0, st); // dt <- step, for the damping of the final boundary call
     }
-    c->stepped = true;
+    c->ls.stepped = true;
 }
 
 void flush_deferred_boundary(fcpt_ctx *c)
 {
-    if (c->bc_deferred) {
-        c->bc_deferred = false;
+    if (c->ls.bc_deferred) {
+        c->ls.bc_deferred = false;
         launch_boundary(c->P, c->stream);
     }
 }
 
-void enqueue_post(fcpt_ctx *c, bool may_defer_boundary)
+void enqueue_post(fcpt_ctx *c, bool may_defer_boundary, const PendingGated *gated)
 {
     join_side(c);
-    // the damping of the final boundary call was applied by k_velocities when damp_in_step
-    const bool damping_done = c->P.damp_in_step != 0 && c->stepped;
-    // fcpt_run_steps: when the call is nothing but the ghost-ring kernel (no separate damping launches, no derived grids
-    // to refresh behind it) and the next launch of the stream is the one-block-per-ring CFL kernel, that launch carries it
-    const bool defer = may_defer_boundary && (damping_done || !c->damp_any) && !(c->P.adiabatic && !c->P.lazy_derived) && cfl_bc_mergeable(c->P);
-    if (c->gated_pending) { // (enqueue_device_step asked the transport to leave its gated fallback launch to this call)
-        c->gated_pending = false;
-        if (!defer && (damping_done || !c->d.damping)) { // the call is nothing but the ghost-ring kernel: one launch for both
-            launch_gated_theta(c->gated, &c->P, c->stream);
-            c->stepped = false;
-            if (c->P.adiabatic && !c->P.lazy_derived) {
-                launch_derived(c->P, c->stream);
-                c->pressure_valid = true;
-            } else {
-                c->pressure_valid = false;
-            }
-            return;
-        }
-        launch_gated_theta(c->gated, nullptr, c->stream);
-    }
-    if (defer)
-        c->bc_deferred = true;
-    else
-        apply_boundary_view(c, c->P, true, damping_done);
-    c->stepped = false;
-    if (c->P.adiabatic && !c->P.lazy_derived) {
-        launch_derived(c->P, c->stream);
-        c->pressure_valid = true;
-    } else {
-        c->pressure_valid = false; // recalculate_derived_disk_quantities: P only, evaluated lazily
-    }
+    const bool gated_pending = gated && gated->pending; // (enqueue_device_step asked the transport to leave its gated fallback launch to this call)
+    const PostPlan plan = plan_post(c->P, step_facts(c), c->ls.stepped, may_defer_boundary, gated_pending);
+    if (gated_pending)
+        launch_gated_theta(gated->launch, plan.with_gated ? &c->P : nullptr, c->stream); // with_gated: one launch for both
+    if (plan.deferred)
+        c->ls.bc_deferred = true;
+    else if (!plan.with_gated)
+        apply_boundary_view(c, c->P, true, plan.damping_done);
+    c->ls.stepped = false;
+    refresh_derived(c);
 }
 
 void enqueue_cfl(fcpt_ctx *c, int apply_policy)
 {
     join_side(c);
-    c->P.qdiff_on = c->qdiff_valid ? 1 : 0;
-    if (c->bc_deferred && !c->cfl_interior && cfl_bc_mergeable(c->P)) {
-        c->bc_deferred = false;
+    c->P.qdiff_on = c->ls.qdiff_valid ? 1 : 0;
+    if (c->ls.bc_deferred && !c->ls.cfl_interior && cfl_bc_mergeable(c->P)) {
+        c->ls.bc_deferred = false;
         launch_cfl_bc(c->P, apply_policy, c->stream); // + the final boundary call of the step before
     } else {
         flush_deferred_boundary(c);
-        launch_cfl(c->P, apply_policy, c->stream, c->cfl_interior);
+        launch_cfl(c->P, apply_policy, c->stream, c->ls.cfl_interior);
     }
-    c->cfl_interior = false;
+    c->ls.cfl_interior = false;
 }
 
 } // namespace fcpt
@@ -296,15 +304,15 @@ int fcpt_cfl_begin(fcpt_ctx *c)
     if (!c)
         return FCPT_EINVAL;
     join_side(c);
-    c->cfl_interior = false;
-    const bool state_final = c->stepped && (!c->damp_any || c->P.damp_in_step != 0); // fcpt_post will not damp
+    c->ls.cfl_interior = false;
+    const bool state_final = c->ls.stepped && (!c->damp_any || c->P.damp_in_step != 0); // fcpt_post will not damp
     if (!state_final)
         return FCPT_OK;
     if (c->P.opt.cfl_split == 0)
         return FCPT_OK;
     ProfScope prof_scope(c);
-    c->P.qdiff_on = c->qdiff_valid ? 1 : 0;
-    c->cfl_interior = launch_cfl_interior(c->P, c->stream);
+    c->P.qdiff_on = c->ls.qdiff_valid ? 1 : 0;
+    c->ls.cfl_interior = launch_cfl_interior(c->P, c->stream);
     HIPCHK(hipGetLastError());
     return FCPT_OK;
 }
@@ -466,14 +474,6 @@ int fcpt_apply_boundary(fcpt_ctx *c, double dt, int32_t final)
 
 } // extern "C"
 namespace {
-unsigned launch_flags(const fcpt_ctx *c)
-{
-    return (c->potential_valid ? 1u : 0u) | (c->pressure_valid ? 2u : 0u) | (c->stepped ? 4u : 0u) |
-           (c->cfl_interior ? 8u : 0u) | (c->kick_energy_b ? 16u : 0u) | (c->fused_source ? 32u : 0u) |
-           (c->march_source ? 64u : 0u) | (c->has_mid ? 128u : 0u) | (c->join_pending ? 256u : 0u) |
-           (c->ghosts_unknown ? 1024u : 0u) | (c->qdiff_valid ? 2048u : 0u) |
-           (c->bc_deferred ? 4096u : 0u) | ((unsigned)c->src_parts << 13);
-}
 bool graph_wanted(const fcpt_ctx *c)
 {
     if (c->profiling || c->graph_failed || c->comm)
@@ -483,37 +483,21 @@ bool graph_wanted(const fcpt_ctx *c)
     // launch-bound grids: the kernels of a step are shorter than the host's launch calls
     return (long long)c->P.nr * c->P.nphi <= 131072;
 }
-// one iteration of the device-resident loop: CFL reduction -> policy kernel -> step -> post
-void enqueue_device_step(fcpt_ctx *c)
+// one iteration of the device-resident loop: CFL reduction -> policy kernel -> step -> post, as plan_device_step() has it
+void enqueue_device_step(fcpt_ctx *c, bool skip_q_store = false)
 {
-    // (built-in: grids below 4 M cells -- measured, profiles/r03_ab_cfl_fold_in_source.txt: 512 x 1536 -2.4 %, 1024 x 3072
-    //  ideal EOS -1.2 %; at 2048 x 4096 the 1 400 workgroups folding 48 KB each cost the kernel what the launch saved)
-    // (the fold of the CFL reduction inside the marching source kernel: Euler steps whose first launch behind the CFL
-    //  reduction -- but for k_potential, which reads no step length -- is that kernel; ring kernel of the reduction in use)
-    const bool frog = c->d.integrator == FCPT_INTEGRATOR_LEAPFROG;
-    const int want = c->P.opt.cfl_fold_in_source;
-    // (fcpt_particles_follow_run_steps with particles: their launch stands between the CFL reduction and the gas step
-    //  and reads the step length, which the fold would leave only in the source kernel's prologue: the policy launch)
-    const bool particles = c->part_follow && c->part.n > 0;
-    const bool fold = (want < 0 ? (long long)c->P.nr * c->P.nphi < (1ll << 22) : want != 0) && !frog && c->fused_source &&
-                      c->march_source && source_march_applies(c->P) && cfl_by_rings(c->P) && !particles;
-    enqueue_cfl(c, fold ? 2 : 1);
-    c->fold_pending = fold;
+    const StepFacts F = step_facts(c);
+    StepPlan plan = plan_device_step(c->P, F);
+    plan.skip_q_store = skip_q_store;
+    enqueue_cfl(c, plan.cfl_policy);
     // the particle step where the reference has it (simulation.cpp:177-180): the step length is in force, the final
     // boundary call of the step before has run (inside the CFL launch or ahead of it), the gas is that of the start of
     // the step
-    if (particles)
+    if (F.particles)
         enqueue_particles_loop(c);
-    {
-        // the gated launch of the fallback transport together with the final boundary call, where that call will be
-        // nothing but the ghost-ring kernel and does not ride in the next CFL launch (grids below 4 M cells)
-        const bool pure_bc = (c->P.damp_in_step != 0 || !c->d.damping) && !(c->P.adiabatic && !c->P.lazy_derived);
-        const bool rides_in_cfl = c->P.opt.bc_in_cfl != 0 && (c->P.damp_in_step != 0 || !c->damp_any) &&
-                                  !(c->P.adiabatic && !c->P.lazy_derived) && cfl_bc_mergeable(c->P);
-        c->want_gated_deferred = c->P.opt.gate_in_boundary != 0 && !frog && pure_bc && !rides_in_cfl;
-    }
-    enqueue_step(c, true, 0.0, c->d.cfl <= 0.8);
-    enqueue_post(c, c->P.opt.bc_in_cfl != 0); // (the boundary call may ride in the next iteration's CFL launch)
+    PendingGated gated;
+    enqueue_step(c, true, 0.0, c->d.cfl <= 0.8, false, plan, &gated);
+    enqueue_post(c, c->P.opt.bc_in_cfl != 0, &gated); // (the boundary call may ride in the next iteration's CFL launch)
 }
 // capture `cycle` steps; true if the host-side state is back where it started (the graph can be replayed)
 bool capture_graph(fcpt_ctx *c, int cycle)
@@ -521,7 +505,7 @@ bool capture_graph(fcpt_ctx *c, int cycle)
     if (!c->capture_stream && hipStreamCreateWithFlags(&c->capture_stream, hipStreamNonBlocking) != hipSuccess)
         return false;
     const Dev P0 = c->P;
-    const unsigned f0 = launch_flags(c);
+    const LaunchState ls0 = c->ls;
     hipStream_t user = c->stream;
     c->stream = c->capture_stream;
     bool ok = hipStreamBeginCapture(c->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
@@ -534,31 +518,20 @@ bool capture_graph(fcpt_ctx *c, int cycle)
     }
     c->stream = user;
     (void)hipGetLastError();
-    const bool periodic = std::memcmp(&P0, &c->P, sizeof(Dev)) == 0 && f0 == launch_flags(c);
+    const bool periodic = std::memcmp(&P0, &c->P, sizeof(Dev)) == 0 && std::memcmp(&ls0, &c->ls, sizeof(LaunchState)) == 0;
     if (ok && periodic)
         ok = hipGraphInstantiate(&c->graph_exec, c->graph, nullptr, nullptr, 0) == hipSuccess;
     if (!ok || !periodic) {
         // nothing was executed during the capture: put the host-side view back and step without a graph
         c->P = P0;
-        c->grid[FCPT_F_SIGMA] = c->P.sigma;
-        c->grid[FCPT_F_VRAD] = c->P.vrad;
-        c->grid[FCPT_F_VAZI] = c->P.vazi;
-        c->grid[FCPT_F_ENERGY] = c->P.energy;
-        c->potential_valid = f0 & 1u;
-        c->pressure_valid = f0 & 2u;
-        c->stepped = f0 & 4u;
-        c->cfl_interior = f0 & 8u;
-        c->kick_energy_b = f0 & 16u;
-        c->ghosts_unknown = f0 & 1024u;
-        c->qdiff_valid = f0 & 2048u;
-        c->bc_deferred = f0 & 4096u;
-        c->src_parts = (int)(f0 >> 13);
+        c->ls = ls0;
+        sync_state_grids(c);
         drop_graph(c);
         return false;
     }
     c->graph_cycle = cycle;
     c->graph_P = c->P;
-    c->graph_flags = f0;
+    c->graph_ls = ls0;
     particles_loop_launch(c, &c->graph_part);
     return true;
 }
@@ -608,58 +581,20 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
                 if (int rc = enqueue_particles_migrate(c))
                     return rc;
             }
-            c->skip_q_store = c->d.integrator != FCPT_INTEGRATOR_LEAPFROG && n + 1 < nsteps; // Q+ / Q- (outputs) by the last step only
-            enqueue_step(c, true, 0.0, c->d.cfl <= 0.8);
+            StepPlan plan;
+            plan.skip_q_store = c->d.integrator != FCPT_INTEGRATOR_LEAPFROG && n + 1 < nsteps; // Q+ / Q- (outputs) by the last step only
+            enqueue_step(c, true, 0.0, c->d.cfl <= 0.8, false, plan);
             if (int rc = enqueue_exchange(c))
                 return rc;
             enqueue_post(c);
         }
         HIPCHK(hipGetLastError());
-    } else if (slabs) {
-        // monitor-time snapping: the reduced dt comes to the host, as in sim::run
-        const double t_final = (double)c->d.nsnapshots * c->d.nmonitor * c->d.monitor_timestep;
-        for (; n < nsteps; ++n) {
-            DevClock k;
-            if (int rc = read_clock(c, &k))
-                return rc;
-            if (t_final > 0 && !(k.time < t_final))
-                break;
-            double cfl_dt, dt, step_dt;
-            if (int rc = fcpt_cfl_allreduce(c, &cfl_dt))
-                return rc;
-            if (int rc = fcpt_calculate_timestep(c, cfl_dt, &dt))
-                return rc;
-            if (int rc = fcpt_snap_to_monitor(c, dt, &step_dt))
-                return rc;
-            const double time_next_monitor = (k.n_monitor + 1) * c->d.monitor_timestep;
-            if (follow_slabs) { // simulation.cpp:177-180 with the indirect term of the last fcpt_set_bodies, then particles::move
-                counted_by_particles_step = true;
-                if (int rc = fcpt_particles_step(c, step_dt, c->P.indirect_x, c->P.indirect_y, c->d.omega_frame * step_dt))
-                    return rc;
-                if (int rc = fcpt_particles_migrate(c))
-                    return rc;
-            }
-            if (int rc = fcpt_step(c, step_dt))
-                return rc;
-            if (int rc = fcpt_exchange(c))
-                return rc;
-            if (int rc = fcpt_post(c, step_dt))
-                return rc;
-            if (int rc = read_clock(c, &k))
-                return rc;
-            if (std::fabs(time_next_monitor - k.time) < 1e-6 * dt) {
-                fcpt_clock hc = {k.time, k.last_dt, k.n_hydro_iter, k.n_monitor + 1, 0};
-                hc.n_snapshot = hc.n_monitor / (uint32_t)(c->d.nmonitor > 0 ? c->d.nmonitor : 1);
-                if (int rc = fcpt_set_clock(c, &hc))
-                    return rc;
-            }
-        }
     } else if (!snap) {
         // dt never leaves the device: CFL reduction -> policy kernel -> step -> post
         if (graph_wanted(c) && nsteps >= 8) {
             join_side(c);
             // A captured cycle is replayed while the host-side state that decided its launches (the whole Dev view, the
-            // lazy-evaluation flags) is what it was at capture: bodies, options, uploads change it for good; the parity
+            // whole LaunchState) is what it was at capture: bodies, options, uploads change it for good; the parity
             // of the transport's ping-pong and the boundary call that rides in the next CFL launch (deferred inside
             // this function only) are put back by one or two plain steps -- the same two that let the lazily evaluated
             // grids settle before the first capture.
@@ -668,7 +603,8 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
             ParticleLaunch part_now;
             particles_loop_launch(c, &part_now);
             auto valid = [&] {
-                return c->graph_exec && std::memcmp(&c->graph_P, &c->P, sizeof(Dev)) == 0 && c->graph_flags == launch_flags(c) &&
+                return c->graph_exec && std::memcmp(&c->graph_P, &c->P, sizeof(Dev)) == 0 &&
+                       std::memcmp(&c->graph_ls, &c->ls, sizeof(LaunchState)) == 0 &&
                        std::memcmp(&c->graph_part, &part_now, sizeof(ParticleLaunch)) == 0;
             };
             for (int lead = 0; lead < 2 && !valid(); ++lead, ++n)
@@ -686,13 +622,14 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
             }
         }
         const bool frog_loop = c->d.integrator == FCPT_INTEGRATOR_LEAPFROG;
-        for (; n < nsteps; ++n) {
-            c->skip_q_store = !frog_loop && n + 1 < nsteps; // Q+ / Q- (outputs) by the last step only
-            enqueue_device_step(c);
-        }
+        for (; n < nsteps; ++n)
+            enqueue_device_step(c, !frog_loop && n + 1 < nsteps); // Q+ / Q- (outputs) by the last step only
         flush_deferred_boundary(c); // the last step's boundary call has no CFL launch to ride in
         HIPCHK(hipGetLastError());
     } else {
+        // monitor-time snapping: the (reduced) dt comes to the host, as in sim::run.  Several slabs: MIN over the slabs,
+        // particles::move behind the particle step, the ghost exchange between the step and its final boundary call
+        const bool particles = slabs ? follow_slabs : follow;
         const double t_final = (double)c->d.nsnapshots * c->d.nmonitor * c->d.monitor_timestep;
         for (; n < nsteps; ++n) {
             DevClock k;
@@ -701,26 +638,31 @@ int fcpt_run_steps(fcpt_ctx *c, int64_t nsteps, int32_t snap, int64_t *done)
             if (t_final > 0 && !(k.time < t_final))
                 break;
             double cfl_dt, dt, step_dt;
-            if (int rc = fcpt_cfl(c, &cfl_dt))
+            if (int rc = slabs ? fcpt_cfl_allreduce(c, &cfl_dt) : fcpt_cfl(c, &cfl_dt))
                 return rc;
             if (int rc = fcpt_calculate_timestep(c, cfl_dt, &dt))
                 return rc;
             if (int rc = fcpt_snap_to_monitor(c, dt, &step_dt))
                 return rc;
             const double time_next_monitor = (k.n_monitor + 1) * c->d.monitor_timestep;
-            if (follow) { // simulation.cpp:177-180, with the indirect term of the last fcpt_set_bodies
+            if (particles) { // simulation.cpp:177-180, with the indirect term of the last fcpt_set_bodies
                 counted_by_particles_step = true;
                 if (int rc = fcpt_particles_step(c, step_dt, c->P.indirect_x, c->P.indirect_y, c->d.omega_frame * step_dt))
                     return rc;
+                if (slabs)
+                    if (int rc = fcpt_particles_migrate(c))
+                        return rc;
             }
             if (int rc = fcpt_step(c, step_dt))
                 return rc;
+            if (slabs)
+                if (int rc = fcpt_exchange(c))
+                    return rc;
             if (int rc = fcpt_post(c, step_dt))
                 return rc;
             if (int rc = read_clock(c, &k))
                 return rc;
-            const bool towrite = std::fabs(time_next_monitor - k.time) < 1e-6 * dt;
-            if (towrite) {
+            if (std::fabs(time_next_monitor - k.time) < 1e-6 * dt) {
                 fcpt_clock hc = {k.time, k.last_dt, k.n_hydro_iter, k.n_monitor + 1, 0};
                 hc.n_snapshot = hc.n_monitor / (uint32_t)(c->d.nmonitor > 0 ? c->d.nmonitor : 1);
                 if (int rc = fcpt_set_clock(c, &hc))

@@ -8,6 +8,7 @@
 // maximum per block (no atomics); k_cfl_final folds the block maxima, applies sqrt and the
 // quotient once, and adds the per-ring FARGO shear limit (:207-220).
 #include "../fcpt_schedule.h" // CFL_ROWS, shared with the chunk planner
+#include "../fcpt_plan.h"     // CFL_MAXP, shared with the step planner
 // One thread owns a phi column and walks CFL_ROWS rings (v_r(i+1) of one ring is v_r(i) of the
 // next, so every value is loaded once); per-block maxima, no atomics.
 template <bool ROWU> __global__ void k_cfl_cells(const Dev P, double *part, int rows)
@@ -93,7 +94,6 @@ template <bool ROWU> __global__ void k_cfl_cells(const Dev P, double *part, int 
 // (CFL_MAXP pairs per thread), sums them (<v_phi>, cfl.cpp:196-205), then evaluates the cells of
 // the ring against that mean (:222-330) -- v_phi is read once instead of once by k_ring_mean and
 // once by k_cfl_cells.  One partial maximum per ring.
-#define CFL_MAXP 8 // pairs of cells per thread (Nphi <= 4096); 16 for rings up to 8192 cells
 // The launch covers rings [r1, r1+n1) and [r2, r2+n2): all of them in one go, or (slabs with neighbours) the
 // interior while the ghost rings are on the wire and the rings next to them after the unpack (fcpt_cfl_begin).
 // k_cfl_final folds the partial maxima.

@@ -637,13 +637,6 @@ void launch_particles_immigrate(const ParticleArgs &A, const ParticleAdaptive &X
 // (and i+1 of v_r); fcpt_exchange_unpack writes rows [0,7) and [nr-7,nr)
 #define CFL_EDGE_LO (FCPT_OVERLAP + 1)
 #define CFL_EDGE_HI (FCPT_OVERLAP + 2)
-bool cfl_by_rings(const Dev &P)
-{
-    // one block per ring: mean and cells in one pass (even Nphi up to 1024 * CFL_MAXP = 8192; the isothermal
-    // viscosity and sound speed per ring, or the lazily derived ones of the ideal EOS)
-    return (P.nphi & 1) == 0 && P.nphi >= 128 && P.nphi <= 1024 * CFL_MAXP && (!P.adiabatic || P.lazy_derived) &&
-           P.stabilize != 2 && P.opt.cfl_rings != 0;
-}
 // rings of 2049 .. 4096 cells: 512 threads with four cell pairs each and ALL their loads ahead of the ring sum, instead
 // of 256 with eight.  Isothermal (two grids): 22.7-23.6 us at 2048 x 4096, the step 0.3187 ms, against 37 us for the
 // 256-thread form and 23.8-25.6 us / 0.3197 ms for 1024 threads with two pairs each (three A/B pairs,
@@ -676,15 +669,7 @@ static void launch_cfl_rings(const Dev &P, int r1, int n1, int r2, int n2, hipSt
     });
 }
 // launch_cfl with the final boundary call of the previous step inside the ring launch (see k_cfl_rings_bc); the caller
-// has checked cfl_bc_mergeable()
-// (worth it only where the ring launch is several rounds of workgroups long -- measured, three / two A/B pairs each,
-//  profiles/r03_ab_bc_in_cfl.txt: 2048 x 4096 isothermal 0.3311 against 0.3343 ms per step, ideal EOS 0.511 against
-//  0.514; on a grid whose workgroups are all resident at once the four waiting ones start with the rest and spin:
-//  512 x 1536 0.0755 against 0.0725, 1024 x 3072 ideal 0.223 against 0.222)
-bool cfl_bc_mergeable(const Dev &P)
-{
-    return cfl_by_rings(P) && P.nr >= 8 && ((long long)P.nr * P.nphi >= (1ll << 22) || P.opt.bc_in_cfl == 2); // (2: tests)
-}
+// has checked cfl_bc_mergeable() (fcpt_plan.cpp)
 // k_cfl_final folds `nparts` partial maxima
 static void launch_cfl_fold(const Dev &P, int nparts, int apply_policy, hipStream_t st)
 {

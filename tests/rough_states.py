@@ -314,7 +314,7 @@ def post_census(d, before, after) -> dict:
 
 
 def _cfl_path(nphi, physics):
-    """The CFL kernels of launch.h:cfl_by_rings: one block per ring (k_cfl_rings) for even rings of 128 .. 1024
+    """The CFL kernels of fcpt_plan.cpp:cfl_by_rings: one block per ring (k_cfl_rings) for even rings of 128 .. 1024
     CFL_MAXP = 8192 cells, else k_ring_mean + k_cfl_cells.  The ideal EOS qualifies through its lazily derived
     quantities, which the marching source kernel implies (Nphi >= 128, fcpt_context.hip); no case here sets
     StabilizeViscosity 2, which would also exclude it."""
