@@ -62,7 +62,7 @@ void options_from_environment(Options &o)
     o.transport_graded = 1;
     o.source_graded = -1;
     o.transport_big = o.transport_ladder = o.transport_rank_grade = -1;
-    o.transport_fallback = o.transport_split = o.fused_source = o.march_source = o.march_source_adi = 1;
+    o.transport_fallback = o.transport_split = o.march_source = o.march_source_adi = 1;
     o.theta_march = o.cfl_rings = o.cfl_split = o.source_ring_parts = o.fused_damping = 1;
     o.cfl_wide_blocks = -1;
     o.gate_in_boundary = 1;
@@ -107,18 +107,8 @@ int dev_upload(fcpt_ctx *c, const double **dst, const std::vector<double> &src)
 void apply_options(fcpt_ctx *c, bool at_create = true)
 {
     const Options &o = c->P.opt;
-    c->ls.fused_source = o.fused_source != 0;
     c->ls.march_source = o.march_source != 0;
-    {
-        // StabilizeViscosity is implemented by the marching kernels and by the per-loop kernels, not by the three
-        // intermediate fused ones: where the march does not run (narrow rings, switched off) fall back to the loops
-        const bool march_runs = c->ls.fused_source && c->ls.march_source && c->P.nphi >= 128 &&
-                                (!c->P.adiabatic || o.march_source_adi != 0);
-        if ((c->P.stabilize || c->P.accel_force) && !march_runs) // (likewise BodyForceFromPotential: no)
-            c->ls.fused_source = c->ls.march_source = false;
-    }
-    const bool adi_march =
-        c->P.adiabatic && c->ls.fused_source && c->ls.march_source && c->P.nphi >= 128 && o.march_source_adi != 0;
+    const bool adi_march = c->P.adiabatic && c->ls.march_source && c->P.nphi >= 128 && o.march_source_adi != 0;
     c->P.lazy_derived = adi_march ? 1 : 0;
     c->P.inline_potential = (adi_march && !c->P.leapfrog && o.inline_potential != 0 && !c->P.accel_force) ? 1 : 0;
     c->P.damp_in_step = (c->damp_foldable && o.fused_damping != 0) ? 1 : 0;
@@ -129,7 +119,7 @@ void apply_options(fcpt_ctx *c, bool at_create = true)
     c->P.sm_sched = nullptr;
     c->P.sm_sched_n = 0;
     c->sm_sched_host.clear();
-    if (c->sm_sched_dev && c->ls.fused_source && c->ls.march_source) {
+    if (c->sm_sched_dev && c->ls.march_source) {
         // (an explicit list, fcpt_set_source_chunks, stands in for the built-in table whatever source_graded says;
         //  source_rows > 0 selects equal chunks over either)
         const std::vector<int> sched = c->sm_lengths.empty() ? source_schedule(c->P, device_cus())
@@ -230,6 +220,7 @@ int alloc_grids(fcpt_ctx *c)
                  {&P.pressure, ns}, {&P.soundspeed, ns}, {&P.scale_height, ns}, {&P.viscosity, ns}, {&P.temperature, ns},
                  {&P.potential, ns},
                  {&P.sigma0, ns}, {&P.vrad0, nv}, {&P.vazi0, ns}, {&P.energy0, ns},
+                 // (qr .. trp: read and written by no kernel; kept allocated, see Dev and profiles/ab_narrow_source.txt)
                  {&P.qr, ns}, {&P.qphi, ns}, {&P.divv, ns}, {&P.trr, ns}, {&P.tpp, ns}, {&P.trp, nv}, {&P.qplus, ns}, {&P.qminus, ns},
                  {&P.rmpA, ns}, {&P.rmmA, ns}, {&P.lpA, ns}, {&P.lmA, ns}, {&P.sigA, ns}, {&P.eA, ns},
                  {&P.rmpB, ns}, {&P.rmmB, ns}, {&P.lpB, ns}, {&P.lmB, ns}, {&P.sigB, ns}, {&P.eB, ns},
@@ -953,7 +944,7 @@ int fcpt_selftest_chunk_tables(int32_t nr, int32_t nphi, int32_t n_cu, int32_t a
     if (nr < 1 || nphi < 1 || n_cu < 8 || damp_inner < 0 || damp_outer < 0 || !n_transport || !n_source || transport_capacity < 0 ||
         source_capacity < 0 || (transport_capacity > 0 && !transport_first_last) || (source_capacity > 0 && !source_seg_first_last))
         return FCPT_EINVAL;
-    Options opt;
+    Options opt{};
     options_from_environment(opt);
     std::vector<int> t, s;
     selftest_chunk_tables(nr, nphi, n_cu, adiabatic != 0, damp_inner, damp_outer, opt, t, s);

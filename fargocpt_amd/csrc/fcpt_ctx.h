@@ -57,7 +57,7 @@ struct LaunchState {
     bool bc_deferred;
     bool has_mid;         // leapfrog: fcpt_set_bodies_midstep gave the bodies at the mid-step time
     bool join_pending;    // fcpt_step_device_begin forked the interior transport to `side`: join_side() is owed
-    bool fused_source, march_source; // the options of these names after apply_options() (StabilizeViscosity may clear them)
+    bool march_source;    // the option of this name after apply_options()
 };
 
 // the gated azimuthal launch of the fallback transport that enqueue_step left to the final boundary call of the step

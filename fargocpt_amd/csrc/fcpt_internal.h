@@ -148,7 +148,7 @@ struct Options {
     int theta_rows;         // ... of k_transport_theta_march
     int transport_fallback; // 1: the two-kernel transport is queued behind every k_transport_fused
     int transport_split;    // fcpt_step_device_begin may split the transport around the ghost exchange
-    int fused_source;       // 0: per-loop source kernels
+    int fused_source_slot;  // no option: keeps the members behind it where they are (see Dev::g_inv_dxt_src)
     int march_source;       // 0: the three fused source kernels instead of the marching one
     int march_source_adi;   // 0: ... for the ideal EOS only
     int theta_march;        // 0: per-pass azimuthal kernels
@@ -169,7 +169,7 @@ struct Options {
 };
 #define FCPT_OPTION_NAMES                                                                                        \
     X(transport_fused) X(transport_rows) X(transport_graded) X(transport_big) X(transport_ladder) X(transport_rank_grade) X(source_rows) X(source_graded) X(theta_rows) X(transport_fallback) X(transport_split)    \
-    X(fused_source) X(march_source) X(march_source_adi) X(theta_march) X(cfl_rings) X(cfl_wide_blocks) X(cfl_fold_in_source) X(gate_in_boundary) X(cfl_split)   \
+    X(march_source) X(march_source_adi) X(theta_march) X(cfl_rings) X(cfl_wide_blocks) X(cfl_fold_in_source) X(gate_in_boundary) X(cfl_split)   \
     X(source_ring_parts) X(fused_damping) X(inline_potential) X(bc_fold) X(bc_in_cfl) X(comm_overlap) X(comm_loopback) X(graph_steps) X(profile_stride)
 
 // Everything a kernel needs: geometry, grids, parameters.  Passed by value.
@@ -182,7 +182,10 @@ struct Dev {
     CArr cs_ring, nu_ring; // isothermal sound speed and alpha-viscosity per ring
     // never filled and read by no kernel (null, as massflow is when unused; their values live in SrcRow): they only keep
     // the members behind them where they are -- without them the compiler allocates the registers of several kernels
-    // differently (VGPRs, SGPR spills, the occupancy of two)
+    // differently (VGPRs, SGPR spills, the occupancy of two).  Likewise the six pointers qr .. trp below (the stored tensors
+    // of the retired per-loop source kernels): without them the ideal-EOS marching kernels and k_cfl_rings_bc compile to
+    // other code; and they stay allocated, because the A/B without the allocations put 512 x 1536 and the headline outside
+    // the parent's range (profiles/ab_narrow_source.txt).  Taking any of it out needs an A/B measurement of its own.
     CArr g_inv_dxt_src, g_inv_rsum, g_inv_drmed2, g_inv_dra2, g_inv_rmsum;
     // per-ring factors (host-evaluated, IEEE):
     //   g_dxtheta = dphi Rmed, g_inv_dxtheta = 1/(dphi Rmed), g_dr_invsurf = (Rsup-Rinf) InvSurf, g_r_omega = Rmed OmegaFrame
@@ -200,8 +203,8 @@ struct Dev {
     double *pressure, *soundspeed, *scale_height, *viscosity, *temperature, *potential;
     // reference (t = 0) copies
     double *sigma0, *vrad0, *vazi0, *energy0;
-    // source-step scratch
-    double *qr, *qphi, *divv, *trr, *tpp, *trp /* (nr+1) rows */, *qplus, *qminus;
+    double *qr, *qphi, *divv, *trr, *tpp, *trp; // placeholders: allocated, used by no kernel (see g_inv_dxt_src)
+    double *qplus, *qminus;                     // Q+ and Q- of SubStep3
     // StabilizeViscosity (viscosity.cpp:256-348): correction factors c1_phi, c1_r; null when it is 0
     double *cfac_phi, *cfac_r;
     double *massflow; // MASSFLOW (data.h:76), (nr+1) rows; null without WriteMassFlow

@@ -15,10 +15,8 @@ namespace fcpt {
 // namespace and template arguments), so that fcpt_profile_stop's table can be matched to profiles/*.csv by name.
 // KID_CLOCK stands for the single-thread k_clock_* kernels (set_dt, scale_dt, advance, policy, policy_ptr, export_cfl).
 enum KernelId {
-    KID_POTENTIAL, KID_SOURCE_VR, KID_SOURCE_VA, KID_COMPRESSION, KID_TW_Q, KID_TW_VA, KID_TW_VR,
-    KID_SN_Q, KID_SN_E, KID_SN_VR, KID_SN_VA, KID_TRANGE, KID_ADI_CS_H, KID_ISO_CS_H,
-    KID_VISCOSITY, KID_PRESSURE, KID_TEMPERATURE, KID_STRESS_DIAG, KID_STRESS_RPHI, KID_VISC_VA,
-    KID_VISC_VR, KID_QPLUS, KID_SUBSTEP3, KID_BOUNDARY, KID_DAMPING, KID_TRANSPORT_RADIAL,
+    KID_POTENTIAL, KID_ADI_CS_H, KID_ISO_CS_H, KID_VISCOSITY, KID_PRESSURE, KID_TEMPERATURE,
+    KID_SUBSTEP3, KID_BOUNDARY, KID_DAMPING, KID_TRANSPORT_RADIAL,
     KID_RING_MEAN, KID_THETA1, KID_THETA2, KID_VELOCITIES, KID_CFL_INIT, KID_CFL_CELLS, KID_CLOCK,
     KID_SRC_FUSED, KID_AV_FUSED, KID_VISC_FUSED, KID_SOURCE_MARCH, KID_THETA_MARCH,
     KID_TRANSPORT_FUSED, KID_MASSFLOW, KID_CFL_RINGS, KID_THETA_GATED_BOUNDARY, KID_EXCHANGE_COPY,
@@ -46,15 +44,10 @@ extern thread_local Profiler *g_prof;
 void launch_potential(const Dev &P, hipStream_t st);
 void launch_accel_on_gas(const Dev &P, hipStream_t st);
 void launch_body_force(const Dev &P, hipStream_t st); // the potential, or the accelerations (simulation.cpp:167-175)
-void launch_source(const Dev &P, hipStream_t st);
-void launch_artificial_viscosity(const Dev &P, hipStream_t st);
 void launch_recalculate_viscosity(const Dev &P, hipStream_t st);
 void launch_viscosity_field(const Dev &P, hipStream_t st);
 void launch_iso_cs_h(const Dev &P, const double *cs_ring, hipStream_t st);
-void launch_stress(const Dev &P, hipStream_t st);
 void launch_visc_factors(const Dev &P, hipStream_t st);
-void launch_viscous_update(const Dev &P, hipStream_t st);
-void launch_substep3(const Dev &P, int update_energy, hipStream_t st);
 void launch_boundary(const Dev &P, hipStream_t st);
 void launch_selftest_half_limiter(int type, long long n, const double *a, const double *b, double *out, hipStream_t st);
 void launch_exchange_copy(const Dev &P, double *inner, double *outer, int unpack, hipStream_t st);

@@ -29,7 +29,7 @@ bool cfl_bc_mergeable(const Dev &P);
 struct StepFacts {
     bool leapfrog;
     bool damping_configured, slab_damped;
-    bool fused_source, march_source; // LaunchState's: the options after apply_options()
+    bool march_source;               // LaunchState's: the option after apply_options()
     bool particles;                  // fcpt_particles_follow_run_steps with particles: their launch stands behind the CFL launch
 };
 

@@ -61,7 +61,6 @@ StepFacts step_facts(const fcpt_ctx *c)
     F.leapfrog = c->d.integrator == FCPT_INTEGRATOR_LEAPFROG;
     F.damping_configured = c->d.damping != 0;
     F.slab_damped = c->damp_any;
-    F.fused_source = c->ls.fused_source;
     F.march_source = c->ls.march_source;
     F.particles = c->part_follow && c->part.n > 0;
     return F;
@@ -76,9 +75,9 @@ void sync_state_grids(fcpt_ctx *c)
     c->grid[FCPT_F_ENERGY] = c->P.energy;
 }
 
+// where a kick left its result: the velocities always in (vrad_b, vazi_b)
 struct KickResult {
-    bool vel_in_b;    // the velocities are in (vrad_b, vazi_b)
-    bool energy_in_b; // ... and the energy in energy_b (marching source step, ideal EOS)
+    bool energy_in_b; // the energy in energy_b (marching source step, ideal EOS)
     int ring_parts;   // segments of ring sums of v_phi left by k_source_march (0: none)
     bool bc_folded;   // the kick applied the boundary conditions that follow it
 };
@@ -89,44 +88,30 @@ struct KickResult {
 KickResult enqueue_kick(fcpt_ctx *c, const Dev &P, bool fold_bc, const StepPlan &plan)
 {
     hipStream_t st = c->stream;
-    KickResult r = {false, false, 0, false};
+    KickResult r = {false, 0, false};
     const bool fold_pending = plan.cfl_policy == 2;
-    if (c->ls.fused_source) {
-        // one pass: (v[, e]) -> (v_b[, e_b])
-        const bool fold_cfl = fold_pending && c->ls.march_source && source_march_applies(P);
-        if (fold_pending && !fold_cfl)
-            launch_cfl_final(P, 1, st);
-        int segs = 0;
-        if (c->ls.march_source && plan.skip_q_store && P.adiabatic && cfl_by_rings(P)) {
-            Dev Q = P; // (Q+ and Q- themselves are read by nothing on the device in this configuration: the ring kernel of the CFL reduction takes their difference)
-            Q.q_skip = 1;
-            segs = launch_source_march(Q, st, fold_bc, &r.bc_folded, fold_cfl);
-        } else if (c->ls.march_source) {
-            segs = launch_source_march(P, st, fold_bc, &r.bc_folded, fold_cfl);
-        }
-        r.vel_in_b = true;
-        r.ring_parts = segs > 0 ? segs : 0;
-        r.energy_in_b = segs != 0 && P.adiabatic;
-        c->ls.qdiff_valid = segs != 0 && P.adiabatic; // the march wrote Q+ - Q- beside Q+ and Q-; the loop kernels do not
-        if (!segs) {
-            ensure_pressure_view(c, P);
-            launch_source_fused(P, st);          // (v) -> (v_b) -> (v)
-            launch_recalculate_viscosity(P, st);
-            launch_viscous_fused(P, st);         // (v) -> (v_b); ideal EOS: + viscous heating + SubStep3
-        }
-        return r;
-    }
-    if (fold_pending)
+    // one pass: (v[, e]) -> (v_b[, e_b])
+    const bool fold_cfl = fold_pending && c->ls.march_source && source_march_applies(P);
+    if (fold_pending && !fold_cfl)
         launch_cfl_final(P, 1, st);
-    c->ls.qdiff_valid = false;
-    ensure_pressure_view(c, P);
-    launch_source(P, st);
-    launch_artificial_viscosity(P, st);
-    launch_recalculate_viscosity(P, st);
-    launch_stress(P, st);
-    launch_viscous_update(P, st);
-    if (P.adiabatic)
-        launch_substep3(P, 1, st);
+    int segs = 0;
+    if (c->ls.march_source && plan.skip_q_store && P.adiabatic && cfl_by_rings(P)) {
+        Dev Q = P; // (Q+ and Q- themselves are read by nothing on the device in this configuration: the ring kernel of the CFL reduction takes their difference)
+        Q.q_skip = 1;
+        segs = launch_source_march(Q, st, fold_bc, &r.bc_folded, fold_cfl);
+    } else if (c->ls.march_source) {
+        segs = launch_source_march(P, st, fold_bc, &r.bc_folded, fold_cfl);
+    }
+    r.ring_parts = segs > 0 ? segs : 0;
+    r.energy_in_b = segs != 0 && P.adiabatic;
+    c->ls.qdiff_valid = segs != 0 && P.adiabatic; // the march wrote Q+ - Q- beside Q+ and Q-; the three fused kernels do not
+    if (!segs) {
+        ensure_pressure_view(c, P);
+        launch_source_fused(P, st);          // (v) -> (v_b) -> (v)
+        launch_recalculate_viscosity(P, st);
+        launch_visc_factors(P, st);          // StabilizeViscosity: from nu and Sigma, for k_visc_fused (1) and the CFL reduction (2)
+        launch_viscous_fused(P, st);         // (v) -> (v_b); ideal EOS: + viscous heating + SubStep3
+    }
     return r;
 }
 
@@ -194,13 +179,11 @@ void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool spl
     const KickResult k1 = enqueue_kick(c, P, !c->ls.ghosts_unknown && !c->ls.stepped, plan);
     c->ls.ghosts_unknown = false;
     Dev Q = P; // view with the post-kick velocities
-    if (k1.vel_in_b) {
-        Q.vrad = P.vrad_b;
-        Q.vazi = P.vazi_b;
-    }
+    Q.vrad = P.vrad_b;
+    Q.vazi = P.vazi_b;
     if (k1.energy_in_b)
         Q.energy = P.energy_b;
-    Q.src_ring_nparts = k1.vel_in_b ? k1.ring_parts : 0; // ring sums of v_phi left by k_source_march
+    Q.src_ring_nparts = k1.ring_parts; // ring sums of v_phi left by k_source_march
     if (!k1.bc_folded) // (else the source march applied it on its edge chunks)
         apply_boundary_view(c, Q, false);
     if (frog)
@@ -242,13 +225,12 @@ void enqueue_step(fcpt_ctx *c, bool dt_dev, double dt, bool shear_safe, bool spl
         Dev K = P;
         K.kick_time_shift = 1; // SubStep3 of the second kick runs at midstep_time (simulation.cpp:388)
         const KickResult k2 = enqueue_kick(c, K, false, StepPlan());
-        if (k2.vel_in_b) { // result in the *_b buffers: bring it home
-            const size_t ns = (size_t)P.nr * P.nphi * sizeof(double), nv = (size_t)(P.nr + 1) * P.nphi * sizeof(double);
-            (void)hipMemcpyAsync(P.vrad, P.vrad_b, nv, hipMemcpyDeviceToDevice, st);
-            (void)hipMemcpyAsync(P.vazi, P.vazi_b, ns, hipMemcpyDeviceToDevice, st);
-            if (k2.energy_in_b)
-                (void)hipMemcpyAsync(P.energy, P.energy_b, ns, hipMemcpyDeviceToDevice, st);
-        }
+        // the result is in the *_b buffers: bring it home
+        const size_t ns = (size_t)P.nr * P.nphi * sizeof(double), nv = (size_t)(P.nr + 1) * P.nphi * sizeof(double);
+        (void)hipMemcpyAsync(P.vrad, P.vrad_b, nv, hipMemcpyDeviceToDevice, st);
+        (void)hipMemcpyAsync(P.vazi, P.vazi_b, ns, hipMemcpyDeviceToDevice, st);
+        if (k2.energy_in_b)
+            (void)hipMemcpyAsync(P.energy, P.energy_b, ns, hipMemcpyDeviceToDevice, st);
         launch_clock_scale_dt(P.clk, 2, 0.0, 1.0, st); // dt <- step, for the damping of the final boundary call
     }
     c->ls.stepped = true;

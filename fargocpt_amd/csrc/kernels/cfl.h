@@ -72,7 +72,7 @@ template <bool ROWU> __global__ void k_cfl_cells(const Dev P, double *part, int 
             if (P.stabilize == 2) { // cfl.cpp:331-351: dt_cell = min(dt_cell, -CFL / c) == CFL / sqrt(max(sum, c^2)), c < 0
                 const double c = dmin(P.cfac_phi[IDX(i, j)], P.cfac_r[IDX(i, j)]);
                 // (the reference tests c != 0.  A positive factor cannot arise: the reference asserts c1_r < 0 and
-                //  c1_phi < 0 where it forms them (viscosity.cpp:339-340), and source_loops.h:386-397 forms the same
+                //  c1_phi < 0 where it forms them (viscosity.cpp:339-340), and visc_factors_row (source_loops.h) forms the same
                 //  expressions; 0 is what nu = 0 and the never-written ring 0 leave)
                 if (c < 0.0)
                     s = dmax(s, c * c);

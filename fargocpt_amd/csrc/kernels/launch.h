@@ -4,10 +4,8 @@
 // ---------------------------------------------------------------------------
 // per-kernel HIP-event timing (fcpt_profile_start/stop)
 const char *const kKernelNames[KID_COUNT] = {
-    "k_potential", "k_source_vr", "k_source_va", "k_compression_heating", "k_tw_q", "k_tw_va", "k_tw_vr",
-    "k_sn_q", "k_sn_e", "k_sn_vr", "k_sn_va", "k_temperature_range", "k_adi_derived", "k_iso_cs_h",
-    "k_viscosity", "k_pressure", "k_temperature", "k_stress_diag", "k_stress_rphi", "k_visc_va",
-    "k_visc_vr", "k_qplus_qminus", "k_substep3", "k_boundary", "k_damping", "k_transport_radial",
+    "k_potential", "k_adi_derived", "k_iso_cs_h", "k_viscosity", "k_pressure", "k_temperature",
+    "k_substep3", "k_boundary", "k_damping", "k_transport_radial",
     "k_ring_mean", "k_transport_theta<1>", "k_transport_theta<2>", "k_velocities", "k_cfl_final",
     "k_cfl_cells", "k_clock", "k_src_fused", "k_av_fused", "k_visc_fused", "k_source_march",
     "k_transport_theta_march", "k_transport_fused", "k_massflow", "k_cfl_rings", "k_theta_march_gated_boundary",
@@ -110,33 +108,6 @@ void launch_body_force(const Dev &P, hipStream_t st)
         launch_potential(P, st);
 }
 
-void launch_source(const Dev &P, hipStream_t st)
-{
-    // update_with_sourceterms, SourceEuler.cpp:435-452
-    LAUNCH2D(KID_SOURCE_VR, k_source_vr, P.maxmo_no_ghost_vr - P.one_no_ghost_vr, P);
-    LAUNCH2D(KID_SOURCE_VA, k_source_va, P.max_no_ghost - P.zero_no_ghost, P);
-    if (P.adiabatic)
-        LAUNCH2D(KID_COMPRESSION, k_compression_heating, P.nr - 1, P);
-}
-
-void launch_artificial_viscosity(const Dev &P, hipStream_t st)
-{
-    // art_visc::update_with_artificial_viscosity, artificial_viscosity.cpp:11-26
-    if (P.art_visc == FCPT_ARTVISC_TW) {
-        LAUNCH2D(KID_TW_Q, k_tw_q, P.nr, P);
-        LAUNCH2D(KID_TW_VA, k_tw_va, P.nr - 2, P);
-        LAUNCH2D(KID_TW_VR, k_tw_vr, P.maxmo_no_ghost_vr - P.one_no_ghost_vr, P);
-    } else if (P.art_visc == FCPT_ARTVISC_SN) {
-        LAUNCH2D(KID_SN_Q, k_sn_q, P.nr, P);
-        if (P.adiabatic && P.art_visc_dissipation)
-            LAUNCH2D(KID_SN_E, k_sn_e, P.max_no_ghost - P.zero_no_ghost, P);
-        LAUNCH2D(KID_SN_VR, k_sn_vr, P.maxmo_no_ghost_vr - P.one_no_ghost_vr, P);
-        LAUNCH2D(KID_SN_VA, k_sn_va, P.max_no_ghost - P.zero_no_ghost, P);
-    }
-    if (P.adiabatic && P.art_visc_dissipation)
-        LAUNCH2D(KID_TRANGE, k_temperature_range, P.nr, P);
-}
-
 void launch_recalculate_viscosity(const Dev &P, hipStream_t st)
 {
     // recalculate_viscosity, SourceEuler.cpp:205-223 (AspectRatioMode 0): c_s, H (and nu when alpha) in one launch;
@@ -154,7 +125,10 @@ void launch_iso_cs_h(const Dev &P, const double *cs_ring, hipStream_t st)
 
 void launch_source_fused(const Dev &P, hipStream_t st)
 {
-    LAUNCH2D(KID_SRC_FUSED, k_src_fused, P.nr + 1, P);
+    if (P.accel_force)
+        LAUNCH2D_T(KID_SRC_FUSED, k_src_fused, true, P.nr + 1, P);
+    else
+        LAUNCH2D_T(KID_SRC_FUSED, k_src_fused, false, P.nr + 1, P);
     LAUNCH2D(KID_AV_FUSED, k_av_fused, P.nr + 1, P);
 }
 // whole source step in one marching pass (Nphi >= 128); returns 0 if not applicable, else +-segments (> 0: ring sums
@@ -226,7 +200,14 @@ int launch_source_march(const Dev &P, hipStream_t st, bool fold_bc, bool *bc_fol
 // stress tensor + viscous update, and for the energy equation viscous heating and -- cell-local, on the Q+ just
 // formed -- SubStep3 (SourceEuler.cpp:956-1051) with the temperature floor / ceiling behind it (the TEMPERATURE grid
 // the reference refreshes there is read by nothing before recalculate_derived_disk_quantities rewrites it)
-void launch_viscous_fused(const Dev &P, hipStream_t st) { LAUNCH2D(KID_VISC_FUSED, k_visc_fused, P.nr + 1, P); }
+// StabilizeViscosity: the factor grids are those of launch_visc_factors, queued ahead by the caller
+void launch_viscous_fused(const Dev &P, hipStream_t st)
+{
+    if (P.stabilize == 1)
+        LAUNCH2D_T(KID_VISC_FUSED, k_visc_fused, true, P.nr + 1, P);
+    else
+        LAUNCH2D_T(KID_VISC_FUSED, k_visc_fused, false, P.nr + 1, P);
+}
 
 // viscosity.cpp:256-348: the correction factors depend on nu and Sigma only
 void launch_visc_factors(const Dev &P, hipStream_t st)
@@ -234,31 +215,11 @@ void launch_visc_factors(const Dev &P, hipStream_t st)
     if (P.stabilize)
         LAUNCH2D(KID_VISC_FACTORS, k_visc_factors, P.nr - 1, P);
 }
-void launch_stress(const Dev &P, hipStream_t st)
-{
-    LAUNCH2D(KID_STRESS_DIAG, k_stress_diag, P.nr, P);
-    LAUNCH2D(KID_STRESS_RPHI, k_stress_rphi, P.nr - 1, P);
-    launch_visc_factors(P, st);
-}
-
-void launch_viscous_update(const Dev &P, hipStream_t st)
-{
-    LAUNCH2D(KID_VISC_VA, k_visc_va, P.nr - 2, P);
-    LAUNCH2D(KID_VISC_VR, k_visc_vr, P.maxmo_no_ghost_vr - P.one_no_ghost_vr, P);
-}
 
 void launch_substep3_cooling_only(const Dev &P, hipStream_t st)
 {
     // compute_heating_cooling_for_CFL at init (SourceEuler.cpp:1507-1547): Q+ = 0 (gas at rest), Q- / alpha
     LAUNCH2D(KID_SUBSTEP3, k_substep3, P.nr, P, 0);
-}
-
-void launch_substep3(const Dev &P, int update_energy, hipStream_t st)
-{
-    // SubStep3, SourceEuler.cpp:956-1051 (update_energy = 1) or the Q+/Q- part of
-    // compute_heating_cooling_for_CFL, :1507-1547 (update_energy = 0)
-    LAUNCH2D(KID_QPLUS, k_qplus_qminus, P.nr, P);
-    LAUNCH2D(KID_SUBSTEP3, k_substep3, P.nr, P, update_energy ? 2 : 0);
 }
 
 // rows [7,14) and [nr-14,nr-7) -> buffers (unpack = 0), buffers -> rows [0,7) and [nr-7,nr) (unpack = 1)
@@ -473,8 +434,7 @@ TransportResult launch_transport(const Dev &P, const Dev &W, hipStream_t st, int
     const bool march = C != 0 && P.opt.theta_march != 0;
     if (march) {
         // the kernel reads the pre-transport v_phi and v_r of a ring (halo columns included) while other
-        // wavefronts already store the new ones: never in place (the per-loop source step leaves its result in
-        // the state grids themselves, the marching one in the *_b twins)
+        // wavefronts already store the new ones: never in place (the source step leaves its result in the *_b twins)
         Dev Wm = W;
         Wm.vrad = P.vrad == W.vrad ? W.vrad_b : W.vrad;
         Wm.vazi = P.vazi == W.vazi ? W.vazi_b : W.vazi;

@@ -9,10 +9,12 @@
 //   k_src_fused : (v_r, v_phi)   -> (v_r_b, v_phi_b)   S1 + S2
 //   k_av_fused  : (v_r_b,v_phi_b)-> (v_r, v_phi) [,e]  S3 + artificial viscosity (+ T range)
 //   k_visc_fused: (v_r, v_phi)   -> (v_r_b, v_phi_b)   stress tensor + viscous update [+ Q+, SubStep3]
-// Row ranges are those of the individual loops; rows outside a range are copied through.
+// Row ranges are those of the reference's loops; rows outside a range are copied through.
 
 // SourceEuler.cpp:325-428 momentum_update_radial + momentum_update_azimuthal
-template <bool ROWU> __global__ void k_src_fused(const Dev P)
+// ACC: BodyForceFromPotential: no -- the bodies' pull from ACCEL_RADIAL / ACCEL_AZIMUTHAL (k_accel_on_gas) instead of the
+// potential's gradient (SourceEuler.cpp:348-353, 406-411)
+template <bool ACC, bool ROWU> __global__ void k_src_fused(const Dev P)
 {
     CELL(0, P.nr + 1);
     const double dt = P.clk->dt;
@@ -22,7 +24,8 @@ template <bool ROWU> __global__ void k_src_fused(const Dev P)
         double gradp = 2.0 / (P.sigma[IDX(i, j)] + P.sigma[IDX(i - 1, j)]);
         gradp *= (P.pressure[IDX(i, j)] - P.pressure[IDX(i - 1, j)]);
         gradp *= P.InvDiffRmed[i];
-        const double gradphi = (P.potential[IDX(i, j)] - P.potential[IDX(i - 1, j)]) * P.InvDiffRmed[i];
+        const double gradphi = ACC ? -(P.accel_r[IDX(i, j)] + P.accel_r[IDX(i - 1, j)]) * 0.5
+                                   : (P.potential[IDX(i, j)] - P.potential[IDX(i - 1, j)]) * P.InvDiffRmed[i];
         const double vsum =
             P.vazi[IDX(i, j)] + P.vazi[IDX(i, jn)] + P.vazi[IDX(i - 1, j)] + P.vazi[IDX(i - 1, jn)];
         const double vt = 0.25 * vsum + P.Rinf[i] * P.omega_frame;
@@ -36,7 +39,8 @@ template <bool ROWU> __global__ void k_src_fused(const Dev P)
             const double invdxtheta = 2.0 / (P.dphi * (P.Rsup[i] + P.Rinf[i]));
             const double gradp = 2.0 / (P.sigma[IDX(i, j)] + P.sigma[IDX(i, jp)]) *
                                  (P.pressure[IDX(i, j)] - P.pressure[IDX(i, jp)]) * invdxtheta;
-            const double gradphi = (P.potential[IDX(i, j)] - P.potential[IDX(i, jp)]) * invdxtheta;
+            const double gradphi = ACC ? -(P.accel_az[IDX(i, j)] + P.accel_az[IDX(i, jp)]) * 0.5
+                                       : (P.potential[IDX(i, j)] - P.potential[IDX(i, jp)]) * invdxtheta;
             va = va + dt * (-gradp - gradphi);
         }
         P.vazi_b[IDX(i, j)] = va;
@@ -184,7 +188,8 @@ __device__ __forceinline__ double tau_rp_at(const Dev &P, int i, int j)
 }
 // compute_viscous_stress_tensor + update_velocities_with_viscosity (viscosity.cpp:139-426)
 // and, for the energy equation, viscous_heating (SourceEuler.cpp:496-536) into QPLUS
-template <bool ROWU> __global__ void k_visc_fused(const Dev P)
+// CORR: StabilizeViscosity 1 -- both velocity increments times visc_corr of the factor grids (k_visc_factors, queued ahead)
+template <bool CORR, bool ROWU> __global__ void k_visc_fused(const Dev P)
 {
     CELL(0, P.nr + 1);
     const double dt = P.clk->dt;
@@ -205,18 +210,20 @@ template <bool ROWU> __global__ void k_visc_fused(const Dev P)
         const TauDiag tjp = tau_diag_at(P, i, jp);
         const double sigma_avg = 0.5 * (P.sigma[IDX(i, j)] + P.sigma[IDX(i, jp)]);
         const double ra1 = P.Rinf[i + 1], ra0 = P.Rinf[i];
-        va += dt * P.InvRmed[i] / (sigma_avg) *
-              ((2.0 / (ra1 * ra1 - ra0 * ra0)) * (ra1 * ra1 * trp_ip - ra0 * ra0 * trp) +
-               (t.tpp - tjp.tpp) * P.invdphi);
+        const double dVp = dt * P.InvRmed[i] / (sigma_avg) *
+                           ((2.0 / (ra1 * ra1 - ra0 * ra0)) * (ra1 * ra1 * trp_ip - ra0 * ra0 * trp) +
+                            (t.tpp - tjp.tpp) * P.invdphi);
+        va += CORR ? dVp * visc_corr(dt, P.cfac_phi[IDX(i, j)]) : dVp;
     }
     double trp_jn = 0.0;
     if (i >= P.one_no_ghost_vr && i < P.maxmo_no_ghost_vr) {
         trp_jn = tau_rp_at(P, i, jn);
         const TauDiag tim = tau_diag_at(P, i - 1, j);
         const double sigma_avg = 0.5 * (P.sigma[IDX(i, j)] + P.sigma[IDX(i - 1, j)]);
-        vr += dt / (sigma_avg)*P.radial_viscosity_factor * 2.0 / (P.Rmed[i] + P.Rmed[i - 1]) *
-              ((P.Rmed[i] * t.trr - P.Rmed[i - 1] * tim.trr) * P.InvDiffRmed[i] + (trp_jn - trp) * P.invdphi -
-               0.5 * (t.tpp + tim.tpp));
+        const double dVr = dt / (sigma_avg)*P.radial_viscosity_factor * 2.0 / (P.Rmed[i] + P.Rmed[i - 1]) *
+                           ((P.Rmed[i] * t.trr - P.Rmed[i - 1] * tim.trr) * P.InvDiffRmed[i] + (trp_jn - trp) * P.invdphi -
+                            0.5 * (t.tpp + tim.tpp));
+        vr += CORR ? dVr * visc_corr(dt, P.cfac_r[IDX(i, j)]) : dVr;
     }
     P.vrad_b[IDX(i, j)] = vr;
     P.vazi_b[IDX(i, j)] = va;

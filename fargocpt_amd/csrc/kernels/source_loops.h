@@ -1,4 +1,4 @@
-// Part of fcpt_kernels.hip (one translation unit, namespace fcpt): potential; one kernel per reference loop nest of the source step; EOS; SubStep3 and its cooling terms.
+// Part of fcpt_kernels.hip (one translation unit, namespace fcpt): potential and body force; EOS and derived grids; StabilizeViscosity factors; SubStep3 and its cooling terms.
 // Not a stand-alone header: included once, in the order given there.
 
 // ---------------------------------------------------------------------------
@@ -76,144 +76,6 @@ template <bool ROWU> __global__ void k_accel_on_gas(const Dev P)
     P.accel_az[IDX(i, j)] = (x * ay - y * ax) / r;
 }
 
-// SourceEuler.cpp:325-372 momentum_update_radial
-template <bool ROWU> __global__ void k_source_vr(const Dev P)
-{
-    CELL(P.one_no_ghost_vr, P.maxmo_no_ghost_vr - P.one_no_ghost_vr);
-    const double dt = P.clk->dt;
-    const int jn = JNEXT;
-    double gradp = 2.0 / (P.sigma[IDX(i, j)] + P.sigma[IDX(i - 1, j)]);
-    gradp *= (P.pressure[IDX(i, j)] - P.pressure[IDX(i - 1, j)]);
-    gradp *= P.InvDiffRmed[i];
-    const double gradphi = P.accel_force ? -(P.accel_r[IDX(i, j)] + P.accel_r[IDX(i - 1, j)]) * 0.5 // :348-353
-                                         : (P.potential[IDX(i, j)] - P.potential[IDX(i - 1, j)]) * P.InvDiffRmed[i];
-    const double vsum =
-        P.vazi[IDX(i, j)] + P.vazi[IDX(i, jn)] + P.vazi[IDX(i - 1, j)] + P.vazi[IDX(i - 1, jn)];
-    const double vt = 0.25 * vsum + P.Rinf[i] * P.omega_frame;
-    const double vt2 = vt * vt;
-    const double centrifugal_accel = vt2 * P.InvRinf[i];
-    P.vrad[IDX(i, j)] += dt * (-gradp - gradphi + centrifugal_accel);
-}
-
-// SourceEuler.cpp:375-428 momentum_update_azimuthal
-template <bool ROWU> __global__ void k_source_va(const Dev P)
-{
-    CELL(P.zero_no_ghost, P.max_no_ghost - P.zero_no_ghost);
-    const double dt = P.clk->dt;
-    const int jp = JPREV;
-    const double invdxtheta = 2.0 / (P.dphi * (P.Rsup[i] + P.Rinf[i]));
-    const double gradp = 2.0 / (P.sigma[IDX(i, j)] + P.sigma[IDX(i, jp)]) *
-                         (P.pressure[IDX(i, j)] - P.pressure[IDX(i, jp)]) * invdxtheta;
-    const double gradphi = P.accel_force ? -(P.accel_az[IDX(i, j)] + P.accel_az[IDX(i, jp)]) * 0.5 // :406-411
-                                         : (P.potential[IDX(i, j)] - P.potential[IDX(i, jp)]) * invdxtheta;
-    P.vazi[IDX(i, j)] = P.vazi[IDX(i, j)] + dt * (-gradp - gradphi);
-}
-
-// SourceEuler.cpp:459-493 compression_heating
-template <bool ROWU> __global__ void k_compression_heating(const Dev P)
-{
-    CELL(0, P.nr - 1);
-    const double dt = P.clk->dt;
-    const int jn = JNEXT;
-    const double DIV_V =
-        (P.vrad[IDX(i + 1, j)] * P.Rinf[i + 1] - P.vrad[IDX(i, j)] * P.Rinf[i]) * P.InvDiffRsupRb[i] +
-        (P.vazi[IDX(i, jn)] - P.vazi[IDX(i, j)]) * P.invdphi * P.InvRmed[i];
-    const double e_old = P.energy[IDX(i, j)];
-    P.energy[IDX(i, j)] = e_old * exp(-(P.gamma - 1.0) * dt * DIV_V);
-}
-
-// viscosity/artificial_viscosity.cpp:48-88 TW: Q_rr, Q_pp (+ dissipation)
-template <bool ROWU> __global__ void k_tw_q(const Dev P)
-{
-    CELL(0, P.nr);
-    const double dt = P.clk->dt;
-    const int jn = JNEXT;
-    const double vr0 = P.vrad[IDX(i, j)], vr1 = P.vrad[IDX(i + 1, j)];
-    const double eps_rr = (vr1 - vr0) * P.InvDiffRsup[i];
-    const double eps_pp =
-        P.InvRmed[i] * ((P.vazi[IDX(i, jn)] - P.vazi[IDX(i, j)]) * P.invdphi + 0.5 * (vr1 + vr0));
-    const double div_V = dmin(eps_rr + eps_pp, 0.0);
-    const double Dr = P.Rinf[i + 1] - P.Rinf[i];
-    const double rDphi = P.Rmed[i] * P.dphi;
-    const double dx = P.nphi <= 16 ? dmin(Dr, rDphi) : dmax(Dr, rDphi);
-    const double l_sq = (P.art_visc_factor * P.art_visc_factor) * (dx * dx);
-    const double rho = P.sigma[IDX(i, j)];
-    P.qr[IDX(i, j)] = l_sq * rho * -div_V * (eps_rr - 1.0 / 3.0 * div_V);
-    P.qphi[IDX(i, j)] = l_sq * rho * -div_V * (eps_pp - 1.0 / 3.0 * div_V);
-    if (P.adiabatic && P.art_visc_dissipation) {
-        if (i > P.zero_no_ghost && i < P.max_no_ghost) {
-            const double Qplus = -l_sq * div_V * rho * 1.0 / 3.0 *
-                                 (eps_rr * eps_rr + eps_pp * eps_pp + (eps_rr - eps_pp) * (eps_rr - eps_pp));
-            P.energy[IDX(i, j)] += Qplus * dt;
-        }
-    }
-}
-// viscosity/artificial_viscosity.cpp:90-117 TW: v_phi
-template <bool ROWU> __global__ void k_tw_va(const Dev P)
-{
-    CELL(1, P.nr - 2);
-    const double dt = P.clk->dt;
-    const int jp = JPREV;
-    const double sigma_phi_avg = 0.5 * (P.sigma[IDX(i, j)] + P.sigma[IDX(i, jp)]);
-    const double dVp = 2.0 * dt / ((P.Rsup[i] + P.Rinf[i]) * sigma_phi_avg) *
-                       (P.qphi[IDX(i, j)] - P.qphi[IDX(i, jp)]) * P.invdphi;
-    P.vazi[IDX(i, j)] += dVp;
-}
-// viscosity/artificial_viscosity.cpp:119-139 TW: v_r
-template <bool ROWU> __global__ void k_tw_vr(const Dev P)
-{
-    CELL(P.one_no_ghost_vr, P.maxmo_no_ghost_vr - P.one_no_ghost_vr);
-    const double dt = P.clk->dt;
-    const double sigma_r_avg = 0.5 * (P.sigma[IDX(i, j)] + P.sigma[IDX(i - 1, j)]);
-    const double rm = P.Rmed[i], rmm = P.Rmed[i - 1];
-    const double dVr = P.radial_viscosity_factor * dt / sigma_r_avg * 2.0 / (rm * rm - rmm * rmm) *
-                       ((P.qr[IDX(i, j)] * rm - P.qr[IDX(i - 1, j)] * rmm) -
-                        0.5 * (P.qphi[IDX(i, j)] + P.qphi[IDX(i - 1, j)]) * (rm - rmm));
-    P.vrad[IDX(i, j)] += dVr;
-}
-// viscosity/artificial_viscosity.cpp:165-189 SN: q_r, q_phi
-template <bool ROWU> __global__ void k_sn_q(const Dev P)
-{
-    CELL(0, P.nr);
-    const int jn = JNEXT;
-    const double C2 = P.art_visc_factor * P.art_visc_factor;
-    const double rho = P.sigma[IDX(i, j)];
-    const double dv_r = P.vrad[IDX(i + 1, j)] - P.vrad[IDX(i, j)];
-    P.qr[IDX(i, j)] = dv_r < 0.0 ? C2 * rho * (dv_r * dv_r) : 0.0;
-    const double dv_phi = P.vazi[IDX(i, jn)] - P.vazi[IDX(i, j)];
-    P.qphi[IDX(i, j)] = dv_phi < 0.0 ? C2 * rho * (dv_phi * dv_phi) : 0.0;
-}
-// viscosity/artificial_viscosity.cpp:194-218 SN: energy dissipation
-template <bool ROWU> __global__ void k_sn_e(const Dev P)
-{
-    CELL(P.zero_no_ghost, P.max_no_ghost - P.zero_no_ghost);
-    const double dt = P.clk->dt;
-    const int jn = JNEXT;
-    const double invdxtheta = 1.0 / (P.dphi * P.Rmed[i]);
-    const double dv_r = P.vrad[IDX(i + 1, j)] - P.vrad[IDX(i, j)];
-    const double dv_phi = P.vazi[IDX(i, jn)] - P.vazi[IDX(i, j)];
-    P.energy[IDX(i, j)] = P.energy[IDX(i, j)] - dt * P.qr[IDX(i, j)] * dv_r * P.InvDiffRsup[i] -
-                          dt * P.qphi[IDX(i, j)] * dv_phi * invdxtheta;
-}
-// viscosity/artificial_viscosity.cpp:220-230 SN: v_r
-template <bool ROWU> __global__ void k_sn_vr(const Dev P)
-{
-    CELL(P.one_no_ghost_vr, P.maxmo_no_ghost_vr - P.one_no_ghost_vr);
-    const double dt = P.clk->dt;
-    P.vrad[IDX(i, j)] = P.vrad[IDX(i, j)] - dt * 2.0 / (P.sigma[IDX(i, j)] + P.sigma[IDX(i - 1, j)]) *
-                                                (P.qr[IDX(i, j)] - P.qr[IDX(i - 1, j)]) * P.InvDiffRmed[i];
-}
-// viscosity/artificial_viscosity.cpp:232-248 SN: v_phi
-template <bool ROWU> __global__ void k_sn_va(const Dev P)
-{
-    CELL(P.zero_no_ghost, P.max_no_ghost - P.zero_no_ghost);
-    const double dt = P.clk->dt;
-    const int jp = JPREV;
-    const double invdxtheta = 1.0 / (P.dphi * P.Rmed[i]);
-    P.vazi[IDX(i, j)] = P.vazi[IDX(i, j)] - dt * 2.0 / (P.sigma[IDX(i, j)] + P.sigma[IDX(i, jp)]) *
-                                                (P.qphi[IDX(i, j)] - P.qphi[IDX(i, jp)]) * invdxtheta;
-}
-
 // SourceEuler.cpp:136-202 assure_temperature_range
 __device__ __forceinline__ double clamp_energy(const Dev &P, double e, double rho)
 {
@@ -236,11 +98,6 @@ __device__ __forceinline__ double clamp_energy_fast(const Dev &P, double e, doub
     if (!(e < e_max))
         e = e_max;
     return e;
-}
-template <bool ROWU> __global__ void k_temperature_range(const Dev P)
-{
-    CELL(0, P.nr);
-    P.energy[IDX(i, j)] = clamp_energy(P, P.energy[IDX(i, j)], P.sigma[IDX(i, j)]);
 }
 
 // SourceEuler.cpp:1054-1092 compute_sound_speed_normal + :1218-1251 compute_scale_height_old
@@ -298,7 +155,7 @@ template <bool ROWU> __global__ void k_temperature(const Dev P)
 // recalculate_derived_disk_quantities (SourceEuler.cpp:225-249) / recalculate_viscosity (:205-223) of the ideal EOS in
 // ONE launch: temperature, sound speed, scale height, pressure, viscosity are pointwise functions of Sigma and e, with
 // the expressions of k_temperature, k_adi_cs_h, k_pressure, k_viscosity.  what: bit 0 temperature, bit 1 pressure
-// (c_s, H and nu always).  Narrow grids run these between the per-loop kernels: four launches of 5 us each were a
+// (c_s, H and nu always).  Narrow grids run these between the fused source kernels: four launches of 5 us each were a
 // fifth of their step.
 template <bool ROWU> __global__ void k_adi_derived(const Dev P, int what)
 {
@@ -320,37 +177,6 @@ template <bool ROWU> __global__ void k_adi_derived(const Dev P, int what)
         P.viscosity[IDX(i, j)] = P.alpha * H * cs;
 }
 
-// viscosity/viscosity.cpp:149-209: div v, tau_rr, tau_phiphi
-template <bool ROWU> __global__ void k_stress_diag(const Dev P)
-{
-    CELL(0, P.nr);
-    const int jn = JNEXT;
-    const double vr0 = P.vrad[IDX(i, j)], vr1 = P.vrad[IDX(i + 1, j)];
-    const double dva = P.vazi[IDX(i, jn)] - P.vazi[IDX(i, j)];
-    const double divv =
-        (vr1 * P.Rinf[i + 1] - vr0 * P.Rinf[i]) * P.InvDiffRsupRb[i] + dva * P.invdphi * P.InvRmed[i];
-    P.divv[IDX(i, j)] = divv;
-    const double nu = P.viscosity[IDX(i, j)], sigma = P.sigma[IDX(i, j)];
-    const double drr = (vr1 - vr0) * P.InvDiffRsup[i];
-    P.trr[IDX(i, j)] = 2.0 * nu * sigma * (drr - 1.0 / 3.0 * divv);
-    const double dpp = dva * P.invdphi * P.InvRmed[i] + 0.5 * (vr1 + vr0) * P.InvRmed[i];
-    P.tpp[IDX(i, j)] = 2.0 * nu * sigma * (dpp - 1.0 / 3.0 * divv);
-}
-// viscosity/viscosity.cpp:211-254: tau_rphi on rows 1..Nr-1 (rows 0 and Nr stay 0)
-template <bool ROWU> __global__ void k_stress_rphi(const Dev P)
-{
-    CELL(1, P.nr - 1);
-    const int jp = JPREV;
-    const double dvazirdr =
-        (P.vazi[IDX(i, j)] * P.InvRmed[i] - P.vazi[IDX(i - 1, j)] * P.InvRmed[i - 1]) * P.InvDiffRmed[i];
-    const double dvrdphi = (P.vrad[IDX(i, j)] - P.vrad[IDX(i, jp)]) * P.invdphi;
-    const double drp = P.Rinf[i] * dvazirdr + dvrdphi * P.InvRinf[i];
-    const double nu = 0.25 * (P.viscosity[IDX(i, j)] + P.viscosity[IDX(i - 1, j)] +
-                              P.viscosity[IDX(i, jp)] + P.viscosity[IDX(i - 1, jp)]);
-    const double sigma = 0.25 * (P.sigma[IDX(i, j)] + P.sigma[IDX(i - 1, j)] + P.sigma[IDX(i, jp)] +
-                                 P.sigma[IDX(i - 1, jp)]);
-    P.trp[IDX(i, j)] = nu * sigma * drp;
-}
 // VISCOSITY_SIGMA_RP (viscosity.cpp:228-252): nu Sigma averaged over the four cells around the corner; rows 0 and Nr hold 0
 __device__ __forceinline__ double nusig_rp(const Dev &P, int i, int j, int jp)
 {
@@ -363,7 +189,9 @@ __device__ __forceinline__ double nusig_rp(const Dev &P, int i, int j, int jp)
     return nu * sigma;
 }
 // viscosity/viscosity.cpp:256-348: correction factors of the pseudo-implicit viscosity (StabilizeViscosity 1|2),
-// rows 1..Nr-1.  Not on the marching path: three small kernels extra per kick.
+// rows 1..Nr-1, for rings the marching kernels do not take (one launch ahead of k_visc_fused) and
+// fcpt_init_physics.  The marching kernels form the same factors in visc_factors_row (source_march.h); this kernel does not
+// call it, because the compiler then rounds the factors differently (measured: other bits in both grids).
 template <bool ROWU> __global__ void k_visc_factors(const Dev P)
 {
     CELL(1, P.nr - 1);
@@ -398,61 +226,6 @@ template <bool ROWU> __global__ void k_visc_factors(const Dev P)
 }
 // viscosity/viscosity.cpp:386-391|413-417: corr = 1 / (max(1 + dt c, 0) - dt c)
 __device__ __forceinline__ double visc_corr(double dt, double c) { return 1.0 / (dmax(1.0 + dt * c, 0.0) - dt * c); }
-// viscosity/viscosity.cpp:368-394: v_phi update
-template <bool ROWU> __global__ void k_visc_va(const Dev P)
-{
-    CELL(1, P.nr - 2);
-    const double dt = P.clk->dt;
-    const int jp = JPREV;
-    const double sigma_avg = 0.5 * (P.sigma[IDX(i, j)] + P.sigma[IDX(i, jp)]);
-    const double ra1 = P.Rinf[i + 1], ra0 = P.Rinf[i];
-    double dVp = dt * P.InvRmed[i] / (sigma_avg) *
-                 ((2.0 / (ra1 * ra1 - ra0 * ra0)) *
-                            (ra1 * ra1 * P.trp[IDX(i + 1, j)] - ra0 * ra0 * P.trp[IDX(i, j)]) +
-                        (P.tpp[IDX(i, j)] - P.tpp[IDX(i, jp)]) * P.invdphi);
-    if (P.stabilize == 1)
-        dVp *= visc_corr(dt, P.cfac_phi[IDX(i, j)]);
-    P.vazi[IDX(i, j)] += dVp;
-}
-// viscosity/viscosity.cpp:396-421: v_r update
-template <bool ROWU> __global__ void k_visc_vr(const Dev P)
-{
-    CELL(P.one_no_ghost_vr, P.maxmo_no_ghost_vr - P.one_no_ghost_vr);
-    const double dt = P.clk->dt;
-    const int jn = JNEXT;
-    const double sigma_avg = 0.5 * (P.sigma[IDX(i, j)] + P.sigma[IDX(i - 1, j)]);
-    double dVr = dt / (sigma_avg)*P.radial_viscosity_factor * 2.0 / (P.Rmed[i] + P.Rmed[i - 1]) *
-                       ((P.Rmed[i] * P.trr[IDX(i, j)] - P.Rmed[i - 1] * P.trr[IDX(i - 1, j)]) * P.InvDiffRmed[i] +
-                        (P.trp[IDX(i, jn)] - P.trp[IDX(i, j)]) * P.invdphi -
-                        0.5 * (P.tpp[IDX(i, j)] + P.tpp[IDX(i - 1, j)]));
-    if (P.stabilize == 1)
-        dVr *= visc_corr(dt, P.cfac_r[IDX(i, j)]);
-    P.vrad[IDX(i, j)] += dVr;
-}
-
-// SourceEuler.cpp:614-630 calculate_qplus + :496-536 viscous_heating and
-// :931-950 calculate_qminus (all cooling terms are out of scope: Q- = 0)
-template <bool ROWU> __global__ void k_qplus_qminus(const Dev P)
-{
-    CELL(0, P.nr);
-    double qplus = 0.0;
-    if (P.heating_viscous && i >= 1 && i < P.nr - 1) {
-        const double nu = P.viscosity[IDX(i, j)];
-        if (nu != 0.0) {
-            const int jn = JNEXT;
-            const double tau_r_phi = 0.25 * (P.trp[IDX(i, j)] + P.trp[IDX(i + 1, j)] + P.trp[IDX(i, jn)] +
-                                             P.trp[IDX(i + 1, jn)]);
-            const double trr = P.trr[IDX(i, j)], tpp = P.tpp[IDX(i, j)], dv = P.divv[IDX(i, j)];
-            const double sigma = P.sigma[IDX(i, j)];
-            double q = 1.0 / (2.0 * nu * sigma) * (trr * trr + 2 * (tau_r_phi * tau_r_phi) + tpp * tpp);
-            q += (2.0 / 9.0) * nu * sigma * (dv * dv);
-            q *= P.heating_viscous_factor;
-            qplus += q;
-        }
-    }
-    P.qplus[IDX(i, j)] = qplus;
-    P.qminus[IDX(i, j)] = 0.0;
-}
 __device__ __forceinline__ double substep3_alpha(const Dev &P, double H, double sigma, double energy)
 {
     const double b = P.mu * (P.gamma - 1.0) / (P.Rgas * sigma);
@@ -641,7 +414,7 @@ __device__ __forceinline__ Cooling cooling_terms(const Dev &P, int i, int j, int
 }
 // SourceEuler.cpp:1000-1048: energy update of SubStep3 (update_energy != 0) or only the
 // alpha rescaling of compute_heating_cooling_for_CFL (:1520-1545)
-// update_energy = 2: followed by SetTemperatureFloorCeilValues on all rings (k_temperature_range) in the same launch
+// update_energy = 2: followed by SetTemperatureFloorCeilValues on all rings (clamp_energy) in the same launch
 // one cell of it; qplus_in / qminus_in: the heating and cooling rates found so far
 __device__ __forceinline__ void substep3_cell(const Dev &P, int i, int j, double qplus_in, double qminus_in, int update_energy)
 {

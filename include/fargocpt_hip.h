@@ -347,7 +347,8 @@ int fcpt_synchronize(fcpt_ctx *ctx);
  * parity-tested kernel variants the step uses, marching-chunk lengths, overlap of the ghost exchange.  The
  * environment variables FCPT_<NAME> only provide the defaults read once in fcpt_create; no launch reads the
  * environment.  -1 = the library's built-in choice.  Names: transport_fused (0 = off, any other value = the built-in choice), transport_rows, transport_graded, transport_big, transport_ladder, transport_rank_grade, source_graded,
- * source_rows, theta_rows, transport_fallback, transport_split, fused_source, march_source, march_source_adi,
+ * source_rows, theta_rows, transport_fallback, transport_split, march_source (0 = the three out-of-place source
+ * kernels instead of the marching one), march_source_adi (the same for the ideal EOS only),
  * theta_march, cfl_rings, cfl_wide_blocks (-1 = built-in: isothermal 512 threads per ring, ideal EOS 256; 0 = 256; any other value = 512),
  * cfl_fold_in_source, gate_in_boundary, cfl_split, source_ring_parts, fused_damping, inline_potential, bc_fold, bc_in_cfl, comm_overlap,
  * comm_loopback, graph_steps, profile_stride (fcpt_profile_start times every n-th launch of the selected kernels).

@@ -33,8 +33,11 @@ def _fields(product, d):
     return _FIELDS[key]
 
 
-def _desc(product, nr=32, nphi=128, adiabatic=False, leapfrog=False, mean=False):
+def _desc(product, nr=32, nphi=128, adiabatic=False, leapfrog=False, mean=False, stab=0, accel=False):
     d = setups.planet_disk(product, nr, nphi, adiabatic=adiabatic)
+    d.stabilize_viscosity = stab
+    if accel:   # BodyForceFromPotential: no
+        d.body_force_from_potential = 0
     if leapfrog:
         d.integrator = B.INTEGRATOR_LEAPFROG
     if mean:   # a mean target: the damping cannot be folded into the transport
@@ -218,7 +221,7 @@ def _slab_loopback(product):
 
 CASES = {"defaults": _simple()}
 for _name, _value in (("bc_in_cfl", 2), ("cfl_fold_in_source", 0), ("gate_in_boundary", 0), ("bc_fold", 0), ("fused_damping", 0),
-                      ("march_source", 0), ("fused_source", 0), ("cfl_rings", 0)):
+                      ("march_source", 0), ("cfl_rings", 0)):
     CASES["%s_%d" % (_name, _value)] = _simple(options=((_name, _value),))
 CASES.update({
     "ideal": _simple(adiabatic=True),
@@ -229,6 +232,12 @@ CASES.update({
     "leapfrog_mid_bodies": _leapfrog_mid(False),
     "leapfrog_ideal_mid_bodies": _leapfrog_mid(True),
     "narrow_24x64": _simple(nr=24, nphi=64),   # neither the source march nor the ring kernel of the CFL reduction
+    # ... per kick k_src_fused, k_av_fused, k_visc_fused; StabilizeViscosity: k_visc_factors ahead of the last;
+    # BodyForceFromPotential: no: k_accel_on_gas in k_potential's place.  These two pin LAUNCHES: with alpha = 1e-3 the
+    # correction of StabilizeViscosity 1 is exactly 1, so the digests of narrow_24x64_stab1 are those of narrow_24x64 --
+    # the arithmetic of k_visc_fused<true,.> is held by the stab1 cases of tests/symmetries.py and test_stabilize_viscosity
+    "narrow_24x64_stab1": _simple(nr=24, nphi=64, stab=1),
+    "narrow_24x64_accel": _simple(nr=24, nphi=64, accel=True),
     "mean_damping": _simple(mean=True),
     # rings of 256 cells, the narrowest that k_transport_fused takes: only there is there a gated launch of its fallback to
     # merge with the final boundary call (k_transport_theta_gated_boundary), or to queue alone where that call rides

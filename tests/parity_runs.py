@@ -13,6 +13,7 @@ TOL = 1e-10
 TOL_DT = 1e-12
 
 SOURCE_MARCH = ("k_source_march", "k_source_march_adi", "k_source_march_adi_wide", "k_source_march_adi_acc")
+SOURCE_FUSED = ("k_src_fused", "k_av_fused", "k_visc_fused")
 TRANSPORT_FUSED = ("k_transport_fused",)
 TRANSPORT_TWO = ("k_transport_radial", "k_transport_radial_means")
 CFL_RINGS = ("k_cfl_rings", "k_cfl_rings_bc")
@@ -133,7 +134,9 @@ def assert_paths(name, opt, prof, fell):
     if opt["src"] == "march":
         assert ran(SOURCE_MARCH) > 0, f"{name}: no marching source kernel ran: {sorted(prof)}"
     else:
-        assert ran(SOURCE_MARCH) == 0, f"{name}: a marching source kernel ran on a per-loop case: {sorted(prof)}"
+        assert ran(SOURCE_MARCH) == 0, f"{name}: a marching source kernel ran on narrow rings: {sorted(prof)}"
+        for k in SOURCE_FUSED:   # "fused": rings narrower than the march takes -- the three out-of-place kernels
+            assert ran((k,)) > 0, f"{name}: {k} did not run: {sorted(prof)}"
     if opt["tr"] in ("fused", "fallback"):
         assert ran(TRANSPORT_FUSED) > 0, f"{name}: k_transport_fused did not run: {sorted(prof)}"
         if opt["tr"] == "fused":

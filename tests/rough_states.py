@@ -310,7 +310,7 @@ def post_census(d, before, after) -> dict:
 # ---------------------------------------------------------------------------------------------------------------
 # the cases of tests/test_gpu_rough_states.py: (id, nr, nphi, physics, kind, options)
 # options: slabs (radial slabs of the HIP run), av, leapfrog, massflow, dt_scale (steps of a multiple of the CFL step),
-#          src: "march" | "loop", tr: "fused" | "two" | "fallback", cfl: "rings" | "cells" | None (not asserted)
+#          src: "march" | "fused" (the three out-of-place kernels of rings the march does not take), tr: "fused" | "two" | "fallback", cfl: "rings" | "cells" | None (not asserted)
 
 
 def _cfl_path(nphi, physics):
@@ -323,7 +323,7 @@ def _cfl_path(nphi, physics):
 
 def _case(nr, nphi, physics, kind, **opt):
     opt.setdefault("slabs", 1)
-    opt.setdefault("src", "march" if nphi >= 128 else "loop")
+    opt.setdefault("src", "march" if nphi >= 128 else "fused")
     opt.setdefault("tr", "fused" if nphi >= 256 else "two")
     opt.setdefault("cfl", _cfl_path(nphi, physics))
     tag = "".join(f"_{k}" for k in ("av", "leapfrog", "massflow") if k in opt and opt[k] not in (False, "TW"))

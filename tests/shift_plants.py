@@ -269,7 +269,7 @@ def _case(name, nr, nphi, physics, plant, classes, **opt):
     opt.setdefault("limiter", "vl")
     opt.setdefault("fast", True)
     opt.setdefault("slabs", 1)
-    opt.setdefault("src", "march" if nphi >= 128 else "loop")
+    opt.setdefault("src", "march" if nphi >= 128 else "fused")
     opt.setdefault("tr", "fused" if nphi >= 256 else "two")
     opt.setdefault("cfl", R._cfl_path(nphi, physics))
     return (name, nr, nphi, physics, opt)

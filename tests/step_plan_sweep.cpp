@@ -39,14 +39,13 @@ static void make(const Case &k, Dev &P, StepFacts &F)
     P.opt.march_source_adi = k.lazy_wanted;
     P.opt.cfl_rings = k.cfl_rings, P.opt.cfl_fold_in_source = k.fold, P.opt.bc_in_cfl = k.bc_in_cfl, P.opt.gate_in_boundary = k.gate;
     const bool march_runs = k.nphi >= 128 && (!k.adiabatic || k.lazy_wanted);
-    const bool sources = !(k.stabilize && !march_runs); // StabilizeViscosity without the march: the per-loop kernels
-    P.lazy_derived = k.adiabatic && sources && march_runs;
+    P.lazy_derived = k.adiabatic && march_runs;
     const bool foldable = k.damping == DAMP_FOLDABLE && !k.leapfrog;
     P.damp_in_step = foldable;
     F.leapfrog = k.leapfrog != 0;
     F.damping_configured = k.damping != DAMP_OFF;
     F.slab_damped = k.damping != DAMP_OFF && k.damping != DAMP_OTHER_SLABS;
-    F.fused_source = F.march_source = sources;
+    F.march_source = true; // the option of this name, at its default
     F.particles = k.particles != 0;
 }
 
@@ -60,7 +59,7 @@ static void check(const Case &k)
     const long long cells = (long long)k.nr * k.nphi, four_m = 1ll << 22;
     // what the kernels can do, restated from their own limits
     const bool ring_kernel = k.nphi % 2 == 0 && k.nphi >= 128 && k.nphi <= 8192 && (!k.adiabatic || P.lazy_derived) && k.stabilize != 2 && k.cfl_rings != 0;
-    const bool march = F.fused_source && F.march_source && k.nphi >= 128 && (!k.adiabatic || k.lazy_wanted);
+    const bool march = F.march_source && k.nphi >= 128 && (!k.adiabatic || k.lazy_wanted);
     const bool merged_kernel = ring_kernel && k.nr >= 8 && (cells >= four_m || k.bc_in_cfl == 2);
     const bool derived_behind = k.adiabatic && !P.lazy_derived;
     const bool damping_launches = F.slab_damped && !P.damp_in_step; // k_damping launches are due in the boundary call

@@ -299,7 +299,7 @@ def _case(name, nr, nphi, physics, kind, transforms, **opt):
     opt.setdefault("steps", 3)
     opt.setdefault("bc", "reflecting")
     opt.setdefault("damp", "reference")
-    opt.setdefault("src", "march" if nphi >= 128 else "loop")
+    opt.setdefault("src", "march" if nphi >= 128 else "fused")
     opt.setdefault("tr", "fused" if nphi >= 256 else "two")
     opt.setdefault("cfl", R._cfl_path(nphi, physics))
     return (name, nr, nphi, physics, kind, tuple(transforms), opt)
@@ -350,6 +350,16 @@ def transformed(lib, t: Transform, d0, radii, fields, bodies):
     d1, radii1 = t.desc(lib, d0)
     return d1, radii1, t.fields(fields), t.bodies(bodies, d0)
 
+
+# rings of 48 cells: a block of the out-of-place kernels is narrower than a wavefront there (their ROWU = false instances);
+# the keywords are those of the 96-column twins.  In both tables below.
+NARROW_48 = [
+    _case("noisy_iso_32x48_stab1", 32, 48, "iso", "noisy", ALL4, stab=1, const_nu=1.0e-2, dt_scale=3.0),
+    _case("shocked_visc_32x48_stab1", 32, 48, "visc", "shocked", MR, stab=1, const_nu=1.0e-2, dt_scale=3.0),
+    _case("noisy_iso_32x48_stab2_rvf", 32, 48, "iso", "noisy", ALL4, stab=2, rvf=2.5, const_nu=1.0e-2),
+    _case("noisy_ideal0_32x48_accel", 32, 48, "ideal0", "noisy", ALL4, accel=True, bc="outflow_zeroshear", damp="mean"),
+    _case("noisy_iso_32x48_accel_lf", 32, 48, "iso", "noisy", ALL4, accel=True, leapfrog=True),
+]
 
 # (id, nr, nphi, physics, kind, transforms, options) -- the census of tests/test_symmetries_oracle.py, all at 32 x 96
 # (one at 32 x 130, the three slabs at 48 x 96): both EOS, TW and SN, leapfrog, both limiters, standard transport, viscous
@@ -402,10 +412,10 @@ ORACLE_CASES = [
     # step in which |Nshift[i] - Nshift[i-1]| > 1; on rings of 320 cells two steps stay at 3.3e-14)
     _case("shift_jump_iso_4cfl", 32, 96, "iso", "shift_jump", ("mirror",), dt_scale=4.0, steps=1),
     _case("shift_jump_iso_32x320_4cfl", 32, 320, "iso", "shift_jump", ("mirror",), dt_scale=4.0, steps=2),
-]
+] + NARROW_48
 
 # the cases of tests/test_gpu_symmetries.py: the smallest rings at which each kernel form still has its seams
-#   96: per-loop source, two-kernel transport;  130: marching source with a ragged third segment, two-kernel transport;
+#   48, 96: the three out-of-place source kernels (48: blocks narrower than a wavefront), two-kernel transport;  130: marching source with a ragged third segment, two-kernel transport;
 #   256: fused transport, CFL by rings;  263: odd fused rings, CFL by cells;  320: six source segments and six fused tiles
 # one case of each marching form steps on explicit ragged chunk lists (set_transport_chunks, set_source_chunks)
 GPU_CASES = [
@@ -438,7 +448,13 @@ GPU_CASES = [
     _case("noisy_iso_32x130_stab1", 32, 130, "iso", "noisy", ALL4, stab=1, const_nu=1.0e-2, dt_scale=3.0),
     _case("noisy_iso_32x130_stab2_rvf", 32, 130, "iso", "noisy", ALL4, stab=2, rvf=2.5, const_nu=1.0e-2, cfl="cells"),
     _case("noisy_iso_40x130_stab2_rvf025", 40, 130, "iso", "noisy", ALL4, stab=2, rvf=0.25, const_nu=1.0e-2, cfl="cells"),
-]
+    # StabilizeViscosity and the accelerations on rings the march does not take: k_visc_factors ahead of k_visc_fused<CORR>,
+    # k_src_fused<ACC> (the ORACLE_CASES of these names)
+    _case("noisy_iso_stab1", 32, 96, "iso", "noisy", ALL4, stab=1, const_nu=1.0e-2, dt_scale=3.0),
+    _case("shocked_visc_stab1", 32, 96, "visc", "shocked", MR, stab=1, const_nu=1.0e-2, dt_scale=3.0),
+    _case("noisy_iso_stab2_rvf", 32, 96, "iso", "noisy", ALL4, stab=2, rvf=2.5, const_nu=1.0e-2),
+    _case("noisy_iso_stab2_rvf025", 32, 96, "iso", "noisy", ALL4, stab=2, rvf=0.25, const_nu=1.0e-2),
+] + NARROW_48
 
 # the cases that also go through fcpt_run_steps, with graph replay: (id of GPU_CASES, transforms)
 DEVICE_LOOP = [

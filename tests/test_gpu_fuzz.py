@@ -92,7 +92,7 @@ def draw(lib, seed):
         _EXTRA["irradiation"] = ([pick(4000.0, 10000.0) / setups.TEMP0_K, pick(0.0, 1500.0) / setups.TEMP0_K],
                                  [4.65e-3, 4.8e-4], [0.0, pick(0.0, 0.01)])
     # appended draw (round 3): BodyForceFromPotential: no -- CalculateAccelOnGas instead of the potential's gradient
-    # (Pframeforce.cpp:96-189), in every source path (marching, per-loop) and integrator
+    # (Pframeforce.cpp:96-189), in every source path (marching, out-of-place) and integrator
     if rng.integers(5) == 0:
         d.body_force_from_potential = 0
     # appended draw (round 3): an explicit, ragged list of chunk lengths for the fused transport kernel (the table path

@@ -94,9 +94,8 @@ def test_tiled_azimuthal_sweep_32x640(product, oracle):
 
 
 def test_unfused_paths_agree(product, oracle, monkeypatch):
-    """The per-loop kernels (FCPT_FUSED_SOURCE=0, FCPT_THETA_MARCH=0) stay available as a
-    cross-check of the fused ones."""
-    monkeypatch.setenv("FCPT_FUSED_SOURCE", "0")
+    """The per-pass azimuthal kernels (FCPT_THETA_MARCH=0) stay available as a cross-check of the
+    marching one."""
     monkeypatch.setenv("FCPT_THETA_MARCH", "0")
     d = setups.planet_disk(product, 48, 96, adiabatic=True)
     _check(run_pair(product, oracle, d, 20), ("sigma", "vrad", "vazi", "energy"))
@@ -384,14 +383,19 @@ def test_irradiation_parity(product, oracle):
     _check(outs, ("sigma", "vrad", "vazi", "energy"))
 
 
-@pytest.mark.parametrize("case", ["update_iso", "update_adiabatic_two_slabs", "dt_leapfrog", "dt_radial_factor",
-                                  "dt_first_step_adiabatic"])
-def test_stabilize_viscosity(product, oracle, case):
+@pytest.mark.parametrize("case", ["update_iso", "update_iso_march_source_0", "update_adiabatic_two_slabs", "dt_leapfrog",
+                                  "dt_radial_factor", "dt_first_step_adiabatic"])
+def test_stabilize_viscosity(product, oracle, case, monkeypatch):
     """StabilizeViscosity 1 (viscosity.cpp:386-391|413-417: the viscous velocity update is damped where
     dt c < -1, forced here by stepping with 3x the CFL step) and 2 (cfl.cpp:331-351: dt <= -CFL / c, binding
     here through the leapfrog's 0.6 on the kinematic limit or a radial viscosity factor): fields, dt history
-    and the correction factors themselves against the oracle, and the switch must change the run."""
+    and the correction factors themselves against the oracle, and the switch must change the run.
+    update_iso_march_source_0: the same rings of 192 cells with the marching kernel switched off -- k_visc_factors and
+    the three out-of-place kernels, as on rings narrower than 128 cells."""
     from fargocpt_amd import driver
+    from tests.parity_runs import SOURCE_MARCH
+    if case.endswith("march_source_0"):
+        monkeypatch.setenv("FCPT_MARCH_SOURCE", "0")
     mode = 1 if case.startswith("update") else 2
     adiabatic = "adiabatic" in case
     d = setups.planet_disk(product, 48, 192, adiabatic=adiabatic)
@@ -428,7 +432,14 @@ def test_stabilize_viscosity(product, oracle, case):
         ctx = driver.make_context(L, dd)
         S = driver.SlabSet([ctx])
         S.prepare()
+        profiled = L is product and case.endswith("march_source_0")
+        if profiled:
+            ctx.profile_start()
         S.run(3)
+        if profiled:   # one kick per step: the factors, then the viscous update that reads them; no marching kernel
+            prof = ctx.profile_stop()
+            ran = lambda names: sum(prof.get(n, (0, 0))[1] for n in names)
+            assert ran(("k_visc_fused",)) == 3 and ran(("k_visc_factors",)) == 3 and ran(SOURCE_MARCH) == 0, sorted(prof)
         facs.append((ctx.download(B.F_VISC_CFAC_PHI), ctx.download(B.F_VISC_CFAC_R)))
         ctx.close()
     assert rel_err(facs[0][0], facs[1][0]) <= TOL and rel_err(facs[0][1], facs[1][1]) <= TOL
@@ -818,7 +829,7 @@ def test_body_force_from_accelerations(product, oracle, case):
     """BodyForceFromPotential: no: CalculateAccelOnGas (Pframeforce.cpp:96-189) fills
     ACCEL_RADIAL / ACCEL_AZIMUTHAL and the source step takes -(a(i) + a(i-1)) / 2 and -(a(j) + a(j-1)) / 2 instead of
     the potential's gradient (SourceEuler.cpp:348-353, 406-411) -- in the marching kernels (a template flag), in the
-    per-loop kernels of narrow rings, with the planet's cubic smoothing, the energy equation, leapfrog (mid-step
+    out-of-place kernels of narrow rings, with the planet's cubic smoothing, the energy equation, leapfrog (mid-step
     bodies) and radial slabs.  The state after N steps and the acceleration grids themselves against the oracle."""
     from fargocpt_amd import driver
     adi = case.startswith("ideal")

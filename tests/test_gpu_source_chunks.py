@@ -194,7 +194,7 @@ CASES = (["iso_tw", "iso_sn_ragged_segment", "iso_noav_constnu_one_chunk", "iso_
 def test_source_chunk_seams_never_change_a_result(product, oracle, case):
     """Two product runs from the same uploaded state, one on the built-in equal chunks and one on an explicit ragged
     table: 12 steps (the march kernel of the case profiled: one launch per step, two under leapfrog -- a fallback to the
-    per-loop kernels cannot pass), bits compared; then the explicit context returns to the built-in choice and both run 4
+    out-of-place kernels cannot pass), bits compared; then the explicit context returns to the built-in choice and both run 4
     more, bits compared again.  State grids, Q+ and Q- (ideal EOS), the correction factors (StabilizeViscosity), and
     (time, last_dt, n_hydro_iter).  The device-loop cases take their first 4 steps profiled (plain launches) and the
     other 8 in one call that may replay a captured graph.  And the explicit run against the oracle at 1e-10."""

@@ -1,7 +1,7 @@
 """The per-ring tables fcpt_create uploads (csrc/fcpt_tables.cpp), bit for bit, without a GPU.
 
 fcpt_selftest_ring_tables returns every table for a descriptor and a slab; `Expect` restates each column in numpy from
-what the per-loop kernels read from the plain geometry arrays (kernels/source_loops.h, transport.h, cfl.h: the
+what the kernels of narrow rings read from the plain geometry arrays (kernels/source_fused.h, transport.h, cfl.h: the
 marching kernels take the same factors from the packed rows), from the row structures' comments in
 csrc/fcpt_internal.h and from the reference's damping ranges (boundary_conditions/damping.cpp:311-427).  Every
 operation is one IEEE double operation in the kernels' order, so the comparison is of bit patterns.  The two columns
@@ -192,14 +192,14 @@ class Expect:
         m = np.arange(-2, nr + 6)
         crow = lambda r: np.clip(r, 0, nr - 1)
         f = {}
-        # A: k_source_vr (pressure gradient of P = Sigma c_s^2 between rings m and m - 1, centrifugal term), k_source_va
+        # A: k_src_fused (pressure gradient of P = Sigma c_s^2 between rings m and m - 1, centrifugal term; v_phi)
         f["cs2_m"] = self.cs[crow(m)] * self.cs[crow(m)]
         f["cs2_m1"] = self.cs[crow(m - 1)] * self.cs[crow(m - 1)]
         f["idr_m"] = _pick(g.InvDiffRmed, m)
         f["rinf_om_m"] = _pick(g.Rinf, m) * d.omega_frame
         f["inv_rinf_m"] = _pick(g.InvRinf, m)
         f["inv_dxt_m"] = _pick(2.0 / (g.dphi * (g.Rsup + g.Rinf)), m, (m >= 0) & (m <= nr))
-        # B: k_tw_q of ring crow(m - 1), and the energy equation's factors of the same ring (k_compression_heating, k_sn_e)
+        # B: tw_q_at of ring crow(m - 1), and the energy equation's factors of the same ring (k_av_fused: compression heating, SN dissipation)
         b = crow(m - 1)
         dr, rdphi = g.Rinf[b + 1] - g.Rinf[b], g.Rmed[b] * g.dphi
         dx = np.minimum(dr, rdphi) if d.nphi <= 16 else np.maximum(dr, rdphi)
@@ -209,7 +209,7 @@ class Expect:
         rb = g.Rmed[b]
         f["inv_omk_b"] = 1.0 / np.sqrt(d.G * d.hydro_center_mass / (rb * rb * rb))
         f["inv_dxtheta_b"] = 1.0 / (g.dphi * rb)
-        # C: k_tw_va, k_tw_vr of ring m - 1
+        # C: the TW velocity updates of k_av_fused on ring m - 1
         c = m - 1
         ok = (c >= 1) & (c <= nr)
         rsum = g.Rsup + g.Rinf
@@ -221,17 +221,17 @@ class Expect:
             f["inv_drmed2_c"] = _pick(1.0 / drmed2, c, ok)
         f["idr_c"] = _pick(g.InvDiffRmed, c)
         f["inv_dxtheta_c"] = _pick(g.InvRmed, c) * g.invdphi
-        # D: k_stress_diag of ring crow(m - 2) ...
+        # D: tau_diag_at of ring crow(m - 2) ...
         dd = crow(m - 2)
         f["rinf_d1"], f["rinf_d0"], f["inv_drsuprb_d"] = g.Rinf[dd + 1], g.Rinf[dd], g.InvDiffRsupRb[dd]
         f["inv_rmed_d"], f["inv_drsup_d"], f["nu_d"] = g.InvRmed[dd], g.InvDiffRsup[dd], self.nu_of(m - 2)
-        # ... and k_stress_rphi of rows 1 .. nr - 1 (ring m - 1): the four-cell mean of a viscosity that is constant along a ring
+        # ... and tau_rp_at of rows 1 .. nr - 1 (ring m - 1): the four-cell mean of a viscosity that is constant along a ring
         ok = (c >= 1) & (c <= nr - 1)
         f["inv_rmed_r"], f["inv_rmed_rm1"] = _pick(g.InvRmed, c, ok), _pick(g.InvRmed, c - 1, ok)
         f["idr_r"], f["rinf_r"], f["inv_rinf_r"] = _pick(g.InvDiffRmed, c, ok), _pick(g.Rinf, c, ok), _pick(g.InvRinf, c, ok)
         nu1, nu2 = self.nu_of(c), self.nu_of(c - 1)
         f["nu_avg_r"] = np.where(ok, 0.25 * (nu1 + nu2 + nu1 + nu2), 0.0)
-        # E: k_visc_va, k_visc_vr of ring m - 2
+        # E: the velocity updates of k_visc_fused on ring m - 2
         k = m - 2
         ok = (k >= 1) & (k <= nr)
         ra1, ra0 = _pick(g.Rinf, k + 1, ok), _pick(g.Rinf, k, ok)
