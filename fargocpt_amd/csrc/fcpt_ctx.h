@@ -34,6 +34,7 @@ using namespace fcpt; // private header of four translation units of namespace-f
 // The particle launch fcpt_run_steps queues in every iteration (fcpt_particles_follow_run_steps), without its per-step
 // scalars, which the kernel takes from the device clock: filled by particles_loop_launch(), launched by
 // enqueue_particles_loop(), and kept beside a captured graph to tell whether the graph still holds that launch.
+// (fcpt_particles_step fills one the same way, with its scalars in A and A.step_offset null, and launches it at once.)
 struct ParticleLaunch {
     int on; // follow is switched on and there are particles; 0: everything below is zero
     int explicit_adaptive, cartesian, adapt_set;

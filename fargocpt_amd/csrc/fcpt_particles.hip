@@ -1,6 +1,8 @@
 // Dust particles of the C ABI: device state, the launch of k_particles_step (kernels/particles.h), the switches of
 // drag and diffusion and the blocking reads.  Replaces particles::integrate with ParticleIntegrator: midpoint (particles/particles.cpp:1525-1557,1579-1672)
 // and ParticleIntegrator: explicit (:1677-2014, k_particles_step_explicit)
+// -- either kernel one template, its host-argument or device-clock form and its slab form chosen by template arguments; one
+// statement of the launch (fill_launch, enqueue_launch) for fcpt_particles_step and for fcpt_run_steps --
 // for one radial slab, and -- fcpt_particles_slabs -- for a slab among several: ownership by window, and particles::move()'s
 // hand-over to the radial neighbours (:2016-2161) as records in messages of the ghost rings' length; see
 // include/fargocpt_hip.h for what is and is not covered.
@@ -174,6 +176,89 @@ bool buffer_on_device(const void *p)
     }
     return a.type == hipMemoryTypeDevice;
 }
+// ---- the launch of a step ---------------------------------------------------------------------------------------------
+// the per-step scalars fcpt_particles_step passes by value; fcpt_run_steps has none (the kernels read the device clock)
+struct StepScalars {
+    double dt, indirect_x, indirect_y, frame_angle;
+    unsigned long long step;
+};
+// the explicit integrator may not step: no step sizes since the last fcpt_particles_set (each caller has its own text)
+bool lacks_step_sizes(const fcpt_ctx *c)
+{
+    return c->part.n > 0 && c->part_integ.kind == 1 && !c->part_adapt_set;
+}
+// The launch of a step from the context as it is.  `host`: its scalars and indirect term (step_offset stays null); null: the
+// device-sourced form of fcpt_run_steps -- dt, frame_angle and the counter stay zero and step_offset is set
+// (kernels/particles.h: particle_dt and its neighbours), the indirect term is the one of the last fcpt_set_bodies.
+// Zero-filled first and copied bytewise: fcpt_run_steps compares two of these with memcmp, padding included.
+void fill_launch(const fcpt_ctx *c, const StepScalars *host, ParticleLaunch *L)
+{
+    std::memset((void *)L, 0, sizeof(*L));
+    L->on = 1;
+    L->explicit_adaptive = c->part_integ.kind == 1;
+    L->cartesian = c->part_integ.cartesian != 0;
+    L->adapt_set = c->part_adapt_set;
+    ParticleArgs &A = L->A;
+    std::memcpy((void *)&A, &c->part, sizeof(A));
+    polar_bodies(c->P, A);
+    A.dt = host ? host->dt : 0.0;
+    A.frame_angle = host ? host->frame_angle : 0.0;
+    A.step = host ? host->step : 0;
+    A.indirect_x = host ? host->indirect_x : c->P.indirect_x;
+    A.indirect_y = host ? host->indirect_y : c->P.indirect_y;
+    A.gas_drag = c->part_diff.gas_drag;
+    A.diffusion = c->part_diff.diffusion;
+    A.id = c->part_id;
+    A.seed = c->part_diff.seed;
+    A.step_offset = host ? nullptr : c->part_step_offset;
+    if (L->explicit_adaptive) {
+        std::memcpy((void *)&L->X, &c->part_adapt, sizeof(L->X));
+        L->X.max_attempts = c->part_integ.max_attempts > 0 ? c->part_integ.max_attempts : kDefaultMaxAttempts;
+        L->X.rmin = c->d.rmin;
+        L->X.rmax = c->d.rmax;
+    }
+}
+// one launch on the context's stream: the explicit or the midpoint kernel, in the slab form where the context is a slab
+void enqueue_launch(fcpt_ctx *c, const ParticleLaunch &L)
+{
+    if (L.explicit_adaptive)
+        launch_particles_explicit(c->P, L.A, L.X, L.cartesian != 0, c->stream, on_slab(c));
+    else
+        launch_particles(c->P, L.A, c->stream, on_slab(c));
+}
+
+// ---- the blocking reads: live slots only, in ascending slot order -----------------------------------------------------
+// The alive bytes of every slot on the host and their count in *m (also when refusing); refuses the caller whose arrays
+// have room for fewer.  on_stream: read behind what the context's stream holds and wait for it; otherwise a blocking copy.
+int live_slots(fcpt_ctx *c, const char *who, int64_t capacity, bool on_stream, std::vector<unsigned char> &alive, int64_t *m)
+{
+    alive.resize((size_t)c->part.n);
+    if (on_stream) {
+        HIPCHK(hipMemcpyAsync(alive.data(), c->part.alive, alive.size(), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    } else {
+        HIPCHK(hipMemcpy(alive.data(), c->part.alive, alive.size(), hipMemcpyDeviceToHost));
+    }
+    *m = 0;
+    for (unsigned char a : alive)
+        *m += a != 0;
+    if (*m > capacity) {
+        set_error("%s: %lld live particles, room for %lld", who, (long long)*m, (long long)capacity);
+        return FCPT_EINVAL;
+    }
+    return FCPT_OK;
+}
+// compaction on download: out[k] = in[slot] over the live slots (null out: that array was not asked for)
+template <class T, class U> void compact(const std::vector<unsigned char> &alive, const T *in, U *out)
+{
+    if (!out)
+        return;
+    size_t k = 0;
+    for (size_t s = 0; s < alive.size(); ++s)
+        if (alive[s])
+            out[k++] = in[s];
+}
+
 int migrate_check(const fcpt_ctx *c, const char *who)
 {
     if (!c) {
@@ -274,7 +359,7 @@ int particles_loop_check(const fcpt_ctx *c)
                   "Leapfrog (switch it off, or use Integrator: Euler)");
         return FCPT_EINVAL;
     }
-    if (c->part.n > 0 && c->part_integ.kind == 1 && !c->part_adapt_set) {
+    if (lacks_step_sizes(c)) {
         set_error("fcpt_run_steps: fcpt_particles_follow_run_steps is on, and the explicit integrator has no step sizes since "
                   "the last fcpt_particles_set: call fcpt_particles_timestep_init or fcpt_particles_adaptive_set first");
         return FCPT_EINVAL;
@@ -282,37 +367,14 @@ int particles_loop_check(const fcpt_ctx *c)
     return FCPT_OK;
 }
 
-// The launch fcpt_particles_step would make from the context as it is, in its device-sourced form: dt, frame_angle and the
-// counter stay zero and step_offset is set (kernels/particles.h: particle_dt and its neighbours); the indirect term is the
-// one of the last fcpt_set_bodies.
+// The launch fcpt_particles_step would make from the context as it is, in its device-sourced form (fill_launch); all zero
+// where follow is off or there are no particles
 void particles_loop_launch(const fcpt_ctx *c, ParticleLaunch *L)
 {
-    std::memset((void *)L, 0, sizeof(*L));
-    if (!c->part_follow || c->part.n <= 0)
-        return;
-    L->on = 1;
-    L->explicit_adaptive = c->part_integ.kind == 1;
-    L->cartesian = c->part_integ.cartesian != 0;
-    L->adapt_set = c->part_adapt_set;
-    ParticleArgs &A = L->A;
-    std::memcpy((void *)&A, &c->part, sizeof(A));
-    polar_bodies(c->P, A);
-    A.dt = 0.0;
-    A.frame_angle = 0.0;
-    A.step = 0;
-    A.indirect_x = c->P.indirect_x;
-    A.indirect_y = c->P.indirect_y;
-    A.gas_drag = c->part_diff.gas_drag;
-    A.diffusion = c->part_diff.diffusion;
-    A.id = c->part_id;
-    A.seed = c->part_diff.seed;
-    A.step_offset = c->part_step_offset;
-    if (L->explicit_adaptive) {
-        std::memcpy((void *)&L->X, &c->part_adapt, sizeof(L->X));
-        L->X.max_attempts = c->part_integ.max_attempts > 0 ? c->part_integ.max_attempts : kDefaultMaxAttempts;
-        L->X.rmin = c->d.rmin;
-        L->X.rmax = c->d.rmax;
-    }
+    if (c->part_follow && c->part.n > 0)
+        fill_launch(c, nullptr, L);
+    else
+        std::memset((void *)L, 0, sizeof(*L));
 }
 
 // the particle step of one iteration of fcpt_run_steps' device loop, behind the launch that left the step length in the clock
@@ -324,10 +386,7 @@ void enqueue_particles_loop(fcpt_ctx *c)
     if (!L.on)
         return;
     join_side(c);
-    if (L.explicit_adaptive)
-        launch_particles_explicit(c->P, L.A, L.X, L.cartesian != 0, c->stream, on_slab(c));
-    else
-        launch_particles(c->P, L.A, c->stream, on_slab(c));
+    enqueue_launch(c, L);
 }
 
 // fcpt_run_steps on several slabs hands the step's leavers over with this (follow on, fcpt_particles_slabs on, a
@@ -479,35 +538,17 @@ int fcpt_particles_step(fcpt_ctx *c, double dt, double indirect_x, double indire
     const unsigned long long step = c->part_diff.step++;
     if (c->part.n <= 0)
         return FCPT_OK;
-    const bool explicit_adaptive = c->part_integ.kind == 1;
-    if (explicit_adaptive && !c->part_adapt_set) {
+    if (lacks_step_sizes(c)) {
         set_error("fcpt_particles_step: the explicit integrator has no step sizes since the last fcpt_particles_set: call "
                   "fcpt_particles_timestep_init or fcpt_particles_adaptive_set first");
         return FCPT_EINVAL;
     }
     join_side(c);
     ProfScope prof_scope(c);
-    ParticleArgs A = c->part;
-    const Dev &P = c->P;
-    polar_bodies(P, A);
-    A.dt = dt;
-    A.indirect_x = indirect_x;
-    A.indirect_y = indirect_y;
-    A.frame_angle = frame_angle;
-    A.gas_drag = c->part_diff.gas_drag;
-    A.diffusion = c->part_diff.diffusion;
-    A.id = c->part_id;
-    A.seed = c->part_diff.seed;
-    A.step = step;
-    if (explicit_adaptive) {
-        ParticleAdaptive X = c->part_adapt;
-        X.max_attempts = c->part_integ.max_attempts > 0 ? c->part_integ.max_attempts : kDefaultMaxAttempts;
-        X.rmin = c->d.rmin;
-        X.rmax = c->d.rmax;
-        launch_particles_explicit(P, A, X, c->part_integ.cartesian != 0, c->stream, on_slab(c));
-    } else {
-        launch_particles(P, A, c->stream, on_slab(c));
-    }
+    const StepScalars host = {dt, indirect_x, indirect_y, frame_angle, step};
+    ParticleLaunch L;
+    fill_launch(c, &host, &L);
+    enqueue_launch(c, L);
     HIPCHK(hipGetLastError());
     return FCPT_OK;
 }
@@ -521,13 +562,8 @@ int fcpt_particles_count(fcpt_ctx *c, int64_t *n_alive)
         return FCPT_OK;
     if (int rc = particles_wait(c, "fcpt_particles_count"))
         return rc;
-    std::vector<unsigned char> alive((size_t)c->part.n);
-    HIPCHK(hipMemcpy(alive.data(), c->part.alive, alive.size(), hipMemcpyDeviceToHost));
-    int64_t m = 0;
-    for (unsigned char a : alive)
-        m += a != 0;
-    *n_alive = m;
-    return FCPT_OK;
+    std::vector<unsigned char> alive;
+    return live_slots(c, "fcpt_particles_count", INT64_MAX, false, alive, n_alive);
 }
 
 int fcpt_particles_get(fcpt_ctx *c, int64_t capacity, uint64_t *id, double *r, double *phi, double *r_dot, double *phi_dot,
@@ -541,33 +577,18 @@ int fcpt_particles_get(fcpt_ctx *c, int64_t capacity, uint64_t *id, double *r, d
     if (int rc = particles_wait(c, "fcpt_particles_get"))
         return rc;
     const size_t nn = (size_t)c->part.n;
-    std::vector<unsigned char> alive(nn);
+    std::vector<unsigned char> alive;
     std::vector<double> host(6 * nn);
     std::vector<unsigned long long> ids(id ? nn : 0);
     if (id)
         HIPCHK(hipMemcpy(ids.data(), c->part_id, nn * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(alive.data(), c->part.alive, nn, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(host.data(), c->part.r, 6 * nn * sizeof(double), hipMemcpyDeviceToHost)); // r is the first of six arrays
-    int64_t m = 0;
-    for (unsigned char a : alive)
-        m += a != 0;
-    *n = m;
-    if (m > capacity) {
-        set_error("fcpt_particles_get: %lld live particles, room for %lld", (long long)m, (long long)capacity);
-        return FCPT_EINVAL;
-    }
+    if (int rc = live_slots(c, "fcpt_particles_get", capacity, false, alive, n))
+        return rc;
     double *out[6] = {r, phi, r_dot, phi_dot, stokes, radius}; // the order of the device block
-    size_t k = 0;
-    for (size_t s = 0; s < nn; ++s) { // compaction on download: ascending slot order
-        if (!alive[s])
-            continue;
-        if (id)
-            id[k] = ids[s];
-        for (int q = 0; q < 6; ++q)
-            if (out[q])
-                out[q][k] = host[q * nn + s];
-        ++k;
-    }
+    compact(alive, ids.data(), id);
+    for (int q = 0; q < 6; ++q)
+        compact(alive, host.data() + q * nn, out[q]);
     return FCPT_OK;
 }
 
@@ -701,34 +722,19 @@ int fcpt_particles_adaptive_get(fcpt_ctx *c, int64_t capacity, double *timestep,
     if (int rc = particles_wait(c, "fcpt_particles_adaptive_get"))
         return rc;
     const size_t nn = (size_t)c->part.n;
-    std::vector<unsigned char> alive(nn);
+    std::vector<unsigned char> alive;
     std::vector<double> host(4 * nn);
     std::vector<unsigned int> counts(2 * nn);
-    HIPCHK(hipMemcpy(alive.data(), c->part.alive, nn, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(host.data(), c->part_adapt.timestep, 4 * nn * sizeof(double), hipMemcpyDeviceToHost)); // the first of four arrays
     HIPCHK(hipMemcpy(counts.data(), c->part_adapt.accepted, 2 * nn * sizeof(unsigned int), hipMemcpyDeviceToHost));
-    int64_t m = 0;
-    for (unsigned char a : alive)
-        m += a != 0;
-    *n = m;
-    if (m > capacity) {
-        set_error("fcpt_particles_adaptive_get: %lld live particles, room for %lld", (long long)m, (long long)capacity);
-        return FCPT_EINVAL;
-    }
+    if (int rc = live_slots(c, "fcpt_particles_adaptive_get", capacity, false, alive, n))
+        return rc;
     double *out[4] = {timestep, facold, r_ddot, phi_ddot};
     uint32_t *cnt[2] = {accepted, rejected};
-    size_t k = 0;
-    for (size_t s = 0; s < nn; ++s) {
-        if (!alive[s])
-            continue;
-        for (int q = 0; q < 4; ++q)
-            if (out[q])
-                out[q][k] = host[q * nn + s];
-        for (int q = 0; q < 2; ++q)
-            if (cnt[q])
-                cnt[q][k] = counts[q * nn + s];
-        ++k;
-    }
+    for (int q = 0; q < 4; ++q)
+        compact(alive, host.data() + q * nn, out[q]);
+    for (int q = 0; q < 2; ++q)
+        compact(alive, counts.data() + q * nn, cnt[q]);
     return FCPT_OK;
 }
 
@@ -746,27 +752,18 @@ int fcpt_particles_normals(fcpt_ctx *c, uint64_t step, int64_t capacity, double 
     }
     launch_particles_normals(c->part.n, c->part_id, c->part_diff.seed, step, d_snv, c->stream);
     std::vector<double> host(nn);
-    std::vector<unsigned char> alive(nn);
+    std::vector<unsigned char> alive;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = hipMemcpyAsync(host.data(), d_snv, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(alive.data(), c->part.alive, nn, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(c->stream);
+    int64_t m = 0;
+    // (alive is read on the stream, behind the kernel and the copy, and the wait covers all three)
+    const int rc = e == hipSuccess ? live_slots(c, "fcpt_particles_normals", capacity, true, alive, &m) : FCPT_OK;
     (void)hipFree(d_snv);
     HIPCHK(e);
-    int64_t m = 0;
-    for (unsigned char a : alive)
-        m += a != 0;
-    if (m > capacity) {
-        set_error("fcpt_particles_normals: %lld live particles, room for %lld", (long long)m, (long long)capacity);
-        return FCPT_EINVAL;
-    }
-    size_t k = 0;
-    for (size_t s = 0; s < nn; ++s)
-        if (alive[s])
-            snv[k++] = host[s];
+    if (rc)
+        return rc;
+    compact(alive, host.data(), snv);
     return FCPT_OK;
 }
 

@@ -502,24 +502,14 @@ void launch_particles(const Dev &P, const ParticleArgs &A, hipStream_t st, bool 
     if (A.n <= 0)
         return;
     const dim3 grid((A.n + 255) / 256), block(256);
-    if (slab) {
-        with_bool(P.adiabatic, [&](auto ADI) {
-            with_bool(A.gas_drag != 0, [&](auto DRAG) {
-                with_bool(A.diffusion != 0, [&](auto DIFF) {
-                    with_bool(A.step_offset != nullptr, [&](auto DEV) {
-                        KLAUNCH(KID_PARTICLES, (k_particles_step<TARG(ADI), TARG(DRAG), TARG(DIFF), TARG(DEV), true>), grid, block, P,
-                                A);
-                    });
-                });
-            });
-        });
-        return;
-    }
     with_bool(P.adiabatic, [&](auto ADI) {
         with_bool(A.gas_drag != 0, [&](auto DRAG) {
             with_bool(A.diffusion != 0, [&](auto DIFF) {
                 with_bool(A.step_offset != nullptr, [&](auto DEV) { // (fcpt_run_steps: per-step scalars from the device clock)
-                    KLAUNCH(KID_PARTICLES, (k_particles_step<TARG(ADI), TARG(DRAG), TARG(DIFF), TARG(DEV)>), grid, block, P, A);
+                    with_bool(slab, [&](auto SLAB) {
+                        KLAUNCH(KID_PARTICLES, (k_particles_step<TARG(ADI), TARG(DRAG), TARG(DIFF), TARG(DEV), TARG(SLAB)>), grid,
+                                block, P, A);
+                    });
                 });
             });
         });
@@ -536,17 +526,13 @@ void launch_particles_explicit(const Dev &P, const ParticleArgs &A, const Partic
     with_bool(P.adiabatic, [&](auto ADI) {
         with_bool(A.gas_drag != 0, [&](auto DRAG) {
             with_bool(cartesian, [&](auto CART) {
-                if (slab && A.step_offset)
-                    KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit_slab_clock<TARG(ADI), TARG(DRAG), TARG(CART)>), grid,
-                            block, P, A, X);
-                else if (slab)
-                    KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit_slab<TARG(ADI), TARG(DRAG), TARG(CART)>), grid, block, P,
-                            A, X);
-                else if (A.step_offset)
-                    KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit_clock<TARG(ADI), TARG(DRAG), TARG(CART)>), grid, block, P,
-                            A, X);
-                else
-                    KLAUNCH(KID_PARTICLES_EXPLICIT, (k_particles_step_explicit<TARG(ADI), TARG(DRAG), TARG(CART)>), grid, block, P, A, X);
+                with_bool(A.step_offset != nullptr, [&](auto DEV) {
+                    with_bool(slab, [&](auto SLAB) {
+                        KLAUNCH(KID_PARTICLES_EXPLICIT,
+                                (k_particles_step_explicit<TARG(ADI), TARG(DRAG), TARG(CART), TARG(DEV), TARG(SLAB)>), grid, block, P, A,
+                                X);
+                    });
+                });
             });
         });
     });

@@ -10,6 +10,8 @@ import pytest
 import fargocpt_amd
 from fargocpt_amd import binding as B, setups
 
+from tests.util import kernel_resource_usage
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -139,26 +141,7 @@ def test_hot_kernel_occupancy_budget():
     """The marching kernels are bound by the vector ALUs and by latency at 3-4 wavefronts per SIMD: their
     register budget is part of the design.  Cross-compiles the kernels for gfx950
     with -Rpass-analysis=kernel-resource-usage and checks occupancy and spills of the bench path."""
-    import shutil
-    import subprocess
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fargocpt_amd", "csrc", "fcpt_kernels.hip")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only",
-                        "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, src],
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    usage, name = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z /\[\]]+): (\d+)", line)
-        if m and name:
-            usage[name][m.group(1).strip()] = int(m.group(2))
+    usage = kernel_resource_usage()
     budget = {  # mangled-name fragment -> (minimum waves per SIMD, scratch bytes per lane allowed)
         "17k_transport_fusedILb0ELb1ELi0E": (4, 0),   # isothermal, damping folded in, van Leer: the bench kernel
         # ideal EOS: 4 waves since round 2 (register diet + waves_per_eu)

@@ -1,9 +1,42 @@
 """Shared helpers of the parity tests."""
 from __future__ import annotations
 
+import functools
+import os
+import re
+import shutil
+import subprocess
+
 import numpy as np
+import pytest
 
 from fargocpt_amd import binding as B, driver
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_resource_usage() -> dict:
+    """{mangled kernel name: {remark: value}} of fcpt_kernels.hip cross-compiled for gfx950 with
+    -Rpass-analysis=kernel-resource-usage ("VGPRs", "TotalSGPRs", "Occupancy [waves/SIMD]", "ScratchSize [bytes/lane]",
+    "VGPRs Spill", ...).  One compilation per process (a result is cached, a skip is not); skips the calling test where
+    hipcc is absent."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "fargocpt_amd", "csrc", "fcpt_kernels.hip")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-c", "--cuda-device-only",
+                        "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, src], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    usage, name = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            usage[name] = {}
+            continue
+        m = re.search(r"remark:\s+([A-Za-z /\[\]]+): (\d+)", line)
+        if m and name:
+            usage[name][m.group(1).strip()] = int(m.group(2))
+    return usage
 
 
 def rel_err(a: np.ndarray, b: np.ndarray) -> float:
