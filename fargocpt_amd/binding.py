@@ -34,6 +34,7 @@ IC_PROFILE, IC_SPREADING_RING, IC_SHOCKTUBE = range(3)
  F_VISC_CFAC_PHI, F_VISC_CFAC_R, F_MASSFLOW, F_ACCEL_RADIAL, F_ACCEL_AZIMUTHAL) = range(21)
 VECTOR_FIELDS = (F_VRAD, F_VRAD0, F_MASSFLOW, F_ACCEL_RADIAL, F_ACCEL_AZIMUTHAL)
 TABLE_SRC, TABLE_RAD, TABLE_THETA, TABLE_DAMP, TABLE_RING, TABLE_DAMP_RANGES, TABLE_AZIMUTH = range(7)
+TABLE_TF = 7
 COMM_ID_BYTES = 128
 
 ERRORS = {-1: "FCPT_EINVAL", -2: "FCPT_ENOMEM", -3: "FCPT_EHIP", -4: "FCPT_ESPLIT", -5: "FCPT_ENODEV", -6: "FCPT_ESHEAR",

@@ -198,6 +198,8 @@ int upload_tables(fcpt_ctx *c, const RingTables &t)
         return rc;
     if (int rc = dev_upload_raw(c, &P.damp_tab, t.damp_rows))
         return rc;
+    if (int rc = dev_upload_raw(c, &P.tf_tab, t.tf))
+        return rc;
     std::memcpy(c->damp, t.damp, sizeof(c->damp));
     c->ring_ref_damped = t.ring_ref_damped;
     c->damp_any = t.damp_any;
@@ -242,8 +244,9 @@ int alloc_grids(fcpt_ctx *c)
         return rc;
     if (int rc = dev_alloc(c, &P.shift_jump, 8))
         return rc;
-    if (int rc = dev_alloc(c, &P.shift_tab, (size_t)nr))
+    if (int rc = dev_alloc(c, &P.shift_tab, (size_t)nr + TF_ROW_GUARD)) // (the guard rows in front of ring 0 stay zero)
         return rc;
+    P.shift_tab += TF_ROW_GUARD;
     c->tf_sched_cap = (size_t)4 * 65536; // graded chunks: two to three rounds of a 512-CU device's wavefront slots, and the padding
     if (int rc = dev_alloc(c, &c->tf_sched_dev, c->tf_sched_cap))
         return rc;

@@ -121,12 +121,41 @@ static_assert(sizeof(SrcRow) == 320, "SrcRow is five 64-byte scalar loads");
 struct alignas(64) ThetaRow { // ring i
     double invsurf, dxtheta, inv_dxtheta, dr_invsurf, invr, r_omega, rmed, pad;
 };
-struct alignas(64) ShiftRow { // ring i, written by k_ring_mean (transport call)
+// ring i, written by k_ring_mean (transport call) and read by k_transport_fused alone: the ring's mean, residual and
+// shift, and every product of them with the step length that is the same for all wavefronts of the transport launch,
+// each rounded as k_transport_fused rounded it when every wavefront formed it for itself.  nr + TF_ROW_GUARD rows, of
+// which Dev::shift_tab is row TF_ROW_GUARD (ring 0): the rows in front stay zero and are what iterations of the
+// marching loop below ring 0 load (they use none of it: a closed interface carries no flux).
+struct alignas(64) ShiftRow {
     double mean, vconst;
     double es, ev, ev_top; // exp(-dt f / tau) of the wave damping: cell-centred, v_r, v_r row i+1 (last ring only)
     int nshift, pad0;
-    double pad1[2];
+    double g_up;   // dt * (dphi Rinf[i+1]): the flux factor of the interface above the ring (RadRow::gphi of k = i + 1)
+    double geo_dt; // ((Rsup - Rinf) InvSurf)[i] * dt
+    double d2u;    // second azimuthal pass, distance factor: (dxtheta - vconst dt) / dxtheta upwind, -(dxtheta + vconst dt) / dxtheta otherwise
+    double gvu;    // geo_dt * vconst
+    int ns;        // nshift modulo Nphi, in [0, Nphi)
+    int dsh;       // sign of ns - ns of ring i-1, folded to the shorter way round the ring: -1, 0, 1 (0 for ring 0)
+    int up2;       // vconst * dt > 0: the second pass is upwind to the left
+    int pad1;
+    double pad2[4];
 };
+static_assert(sizeof(ShiftRow) == 128, "ShiftRow is two 64-byte scalar loads");
+#define TF_ROW_GUARD 5 // rows in front of ring 0 in the two per-iteration tables of k_transport_fused: ring i = m - 2 of iteration m = -3 is ring -5
+// Everything iteration m of k_transport_fused reads that no step changes (interface k = m - 1, ring i = m - 2, and the
+// ring m + 1 that the bottom of the iteration converts), stored at index m + 3 for m = -3 .. nr + 1: the values the
+// kernel's clamped loads of RadRow, ThetaRow and DampRow returned, so that the loop clamps nothing and advances one
+// pointer.  The first 96 bytes are what the loop reads; gphi and dr_invsurf are k_ring_mean's (ShiftRow::g_up, geo_dt).
+struct alignas(64) TfRow {
+    double dr_lo, dr_hi, idr_up;                         // RadRow of interface max(k, -1)
+    double invsurf, dxtheta, inv_dxtheta, invr, r_omega; // ThetaRow of ring i (of ring 0 where i is outside the grid)
+    double r_next, romega_next;                          // ThetaRow::rmed, r_omega of ring m + 1 (of ring 0 outside the grid)
+    int tvr, tva, tsg, ten;                              // DampRow types of ring i (of ring 0 outside the grid)
+    double gphi;                                         // RadRow::gphi of interface max(k, -1)
+    double dr_invsurf;                                   // ThetaRow::dr_invsurf of ring i
+    double pad[2];
+};
+static_assert(sizeof(TfRow) == 128, "TfRow is two 64-byte scalar loads");
 struct alignas(64) DampRow { // ring i (nr + 1 rows: v_r has row nr)
     double fs, ts, fv, tv;
     int tvr, tva, tsg, ten;
@@ -148,7 +177,7 @@ struct Options {
     int theta_rows;         // ... of k_transport_theta_march
     int transport_fallback; // 1: the two-kernel transport is queued behind every k_transport_fused
     int transport_split;    // fcpt_step_device_begin may split the transport around the ghost exchange
-    int fused_source_slot;  // no option: keeps the members behind it where they are (see Dev::g_inv_dxt_src)
+    int fused_source_slot;  // no option: keeps the members behind it where they are (see Dev::g_inv_rsum)
     int march_source;       // 0: the three fused source kernels instead of the marching one
     int march_source_adi;   // 0: ... for the ideal EOS only
     int theta_march;        // 0: per-pass azimuthal kernels
@@ -186,7 +215,9 @@ struct Dev {
     // of the retired per-loop source kernels): without them the ideal-EOS marching kernels and k_cfl_rings_bc compile to
     // other code; and they stay allocated, because the A/B without the allocations put 512 x 1536 and the headline outside
     // the parent's range (profiles/ab_narrow_source.txt).  Taking any of it out needs an A/B measurement of its own.
-    CArr g_inv_dxt_src, g_inv_rsum, g_inv_drmed2, g_inv_dra2, g_inv_rmsum;
+    // (the first of these slots now holds the per-iteration table of k_transport_fused: a pointer for a pointer)
+    const TfRow *tf_tab; // nr + TF_ROW_GUARD rows, row m + 3 = iteration m
+    CArr g_inv_rsum, g_inv_drmed2, g_inv_dra2, g_inv_rmsum;
     // per-ring factors (host-evaluated, IEEE):
     //   g_dxtheta = dphi Rmed, g_inv_dxtheta = 1/(dphi Rmed), g_dr_invsurf = (Rsup-Rinf) InvSurf, g_r_omega = Rmed OmegaFrame
     CArr g_dxtheta, g_inv_dxtheta, g_dr_invsurf, g_r_omega;
@@ -203,7 +234,7 @@ struct Dev {
     double *pressure, *soundspeed, *scale_height, *viscosity, *temperature, *potential;
     // reference (t = 0) copies
     double *sigma0, *vrad0, *vazi0, *energy0;
-    double *qr, *qphi, *divv, *trr, *tpp, *trp; // placeholders: allocated, used by no kernel (see g_inv_dxt_src)
+    double *qr, *qphi, *divv, *trr, *tpp, *trp; // placeholders: allocated, used by no kernel (see g_inv_rsum)
     double *qplus, *qminus;                     // Q+ and Q- of SubStep3
     // StabilizeViscosity (viscosity.cpp:256-348): correction factors c1_phi, c1_r; null when it is 0
     double *cfac_phi, *cfac_r;
@@ -347,6 +378,7 @@ struct RingTables {
     std::vector<double> fs, ts, fv, tv;     // nr + 1: Dev::dfac_s, dtau_s, dfac_v, dtau_v
     std::vector<int> dtype[4];              // nr + 1: Dev::dtype_vr, dtype_va, dtype_sig, dtype_e
     std::vector<DampRow> damp_rows;         // nr + 1
+    std::vector<TfRow> tf;                  // nr + TF_ROW_GUARD
     std::vector<int> ring_ref_damped;       // nr: 1 where a folded damping loads reference values
     bool damp_any = false;                  // this slab holds rings of a damping zone
     bool damp_foldable = false;             // ... and its damping can be folded into the transport (no "mean" target, Euler)
@@ -357,6 +389,9 @@ int validate_create(const fcpt_desc *d, const double *radii);
 double omega_kepler(const fcpt_desc &d, double r); // sqrt(G M / r^3)
 DampRange damp_range(const fcpt_desc &d, const fcpt_split &s, const HostGeometry &g, int is_vector, int type, int outer);
 void build_ring_tables(const fcpt_desc &d, const fcpt_split &s, const HostGeometry &g, RingTables &t);
+// the per-iteration rows of k_transport_fused from the per-type rows (build_ring_tables calls it last)
+void build_tf_rows(int nr, const std::vector<RadRow> &rad, const std::vector<ThetaRow> &theta, const std::vector<DampRow> &damp,
+                   std::vector<TfRow> &rows);
 // the descriptor's and the split's scalars, and the default body (the central star at the origin)
 void fill_parameters(const fcpt_desc &d, const fcpt_split &s, const HostGeometry &g, Dev &P);
 

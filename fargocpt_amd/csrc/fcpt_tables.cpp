@@ -279,12 +279,37 @@ void build_damping(const fcpt_desc &d, const fcpt_split &s, const HostGeometry &
 
 } // namespace
 
+// per-iteration rows of k_transport_fused: for iteration m (interface k = m - 1, ring i = m - 2, next ring m + 1) the
+// fields of the per-type rows at the indices the kernel's clamped loads used -- interface max(k, -1), ring i and ring
+// m + 1 replaced by ring 0 where they lie outside the grid
+void build_tf_rows(int nr, const std::vector<RadRow> &rad, const std::vector<ThetaRow> &theta, const std::vector<DampRow> &damp,
+                   std::vector<TfRow> &rows)
+{
+    rows.resize((size_t)nr + TF_ROW_GUARD);
+    for (int m = -3; m <= nr + 1; ++m) {
+        const int k = m - 1, i = m - 2;
+        const RadRow &rk = rad[(size_t)((k < -1 ? -1 : k) + 1)];
+        const int ic = (i >= 0 && i < nr) ? i : 0;
+        const ThetaRow &ti = theta[(size_t)ic];
+        const ThetaRow &tn = theta[(size_t)((m + 1 >= 0 && m + 1 < nr) ? m + 1 : 0)];
+        const DampRow &di = damp[(size_t)ic];
+        TfRow &R = rows[(size_t)(m + 3)];
+        std::memset(&R, 0, sizeof(R));
+        R.dr_lo = rk.dr_lo, R.dr_hi = rk.dr_hi, R.idr_up = rk.idr_up, R.gphi = rk.gphi;
+        R.invsurf = ti.invsurf, R.dxtheta = ti.dxtheta, R.inv_dxtheta = ti.inv_dxtheta, R.invr = ti.invr, R.r_omega = ti.r_omega;
+        R.dr_invsurf = ti.dr_invsurf;
+        R.r_next = tn.rmed, R.romega_next = tn.r_omega;
+        R.tvr = di.tvr, R.tva = di.tva, R.tsg = di.tsg, R.ten = di.ten;
+    }
+}
+
 void build_ring_tables(const fcpt_desc &d, const fcpt_split &s, const HostGeometry &g, RingTables &t)
 {
     build_plain_arrays(d, s, g, t);
     build_rad_theta_rows(s, g, t);
     build_src_rows(d, s, g, t);
     build_damping(d, s, g, t);
+    build_tf_rows(s.nr, t.rad, t.theta, t.damp_rows, t.tf);
 }
 
 void fill_parameters(const fcpt_desc &d, const fcpt_split &s, const HostGeometry &g, Dev &P)
@@ -415,6 +440,11 @@ int table_columns(const RingTables &t, int nr, int table, std::vector<double> &v
         for (size_t j = 0; j < t.cosphi.size(); ++j)
             v.insert(v.end(), {t.cosphi[j], t.sinphi[j]});
         return 2;
+    case FCPT_TABLE_TF:
+        for (const TfRow &r : t.tf)
+            v.insert(v.end(), {r.dr_lo, r.dr_hi, r.idr_up, r.invsurf, r.dxtheta, r.inv_dxtheta, r.invr, r.r_omega, r.r_next, r.romega_next,
+                               (double)r.tvr, (double)r.tva, (double)r.tsg, (double)r.ten, r.gphi, r.dr_invsurf});
+        return 16;
     }
     return 0;
 }

@@ -286,6 +286,15 @@ __device__ __forceinline__ void ring_mean_block(const Dev &P, int vb, int with_s
     int my_shift = 0;
     if (active) {
         const double invr = P.InvRmed[i], rmed = P.Rmed[i];
+        // the static factors of the ring's step products (ShiftRow), requested with the ring's other scalars: TfRow of
+        // iteration i + 2 holds ring i and the interface above it
+        double gphi_up = 0.0, dr_invsurf = 0.0, dxtheta = 0.0, inv_dxtheta = 0.0;
+        if (with_shift) {
+            typedef const double __attribute__((address_space(4))) *cdptr;
+            const cdptr tf = (cdptr)(const void *)(P.tf_tab + (i + TF_ROW_GUARD));
+            gphi_up = tf[offsetof(TfRow, gphi) / sizeof(double)], dr_invsurf = tf[offsetof(TfRow, dr_invsurf) / sizeof(double)];
+            dxtheta = tf[offsetof(TfRow, dxtheta) / sizeof(double)], inv_dxtheta = tf[offsetof(TfRow, inv_dxtheta) / sizeof(double)];
+        }
         const double acc = ring_sum_vphi(P, i, lane, part, nparts, pstride);
         if (with_shift) { // (all lanes: the shift is needed wave-uniform below)
             const double mean0 = __shfl(acc, 0, 64) / (double)P.nphi;
@@ -304,7 +313,25 @@ __device__ __forceinline__ void ring_mean_block(const Dev &P, int vb, int with_s
                 const double vc = (Ntilde - Nround) * rmed * invdt * P.dphi;
                 P.vconst[i] = vc;
                 ShiftRow sr;
-                sr.mean = mean, sr.vconst = vc, sr.nshift = (int)Nround, sr.pad0 = 0, sr.pad1[0] = sr.pad1[1] = 0.0;
+                sr.mean = mean, sr.vconst = vc, sr.nshift = (int)Nround, sr.pad0 = 0, sr.pad1 = 0;
+                sr.pad2[0] = sr.pad2[1] = sr.pad2[2] = sr.pad2[3] = 0.0;
+                // What every wavefront of k_transport_fused formed from this row and dt for itself, each product and sum
+                // rounded once as there (the kernel had v_mul_f64 and v_add_f64, no fused form; the empty asm statements
+                // keep the compiler from contracting them here).
+                double ksi = vc * dt; // (theta_pass of the second azimuthal pass: vu * dt)
+                asm volatile("" : "+v"(ksi));
+                sr.up2 = ksi > 0.0 ? 1 : 0;
+                double span = sr.up2 ? dxtheta - ksi : dxtheta + ksi;
+                asm volatile("" : "+v"(span));
+                sr.d2u = sr.up2 ? span * inv_dxtheta : -span * inv_dxtheta;
+                double geo_dt = dr_invsurf * dt;
+                asm volatile("" : "+v"(geo_dt));
+                sr.geo_dt = geo_dt;
+                sr.gvu = geo_dt * vc;
+                sr.g_up = dt * gphi_up;
+                const int nsm = (int)Nround % P.nphi;
+                sr.ns = nsm < 0 ? nsm + P.nphi : nsm;
+                sr.dsh = 0; // (ring 0; the others below, once the previous ring's shift is here)
                 const DampRow dr = P.damp_tab[i]; // damping.cpp:311-427: X <- (X - X0) exp(-dt f / tau) + X0
                 sr.es = exp(-dt * dr.fs / dr.ts);
                 sr.ev = exp(-dt * dr.fv / dr.tv);
@@ -339,6 +366,13 @@ __device__ __forceinline__ void ring_mean_block(const Dev &P, int vb, int with_s
     dd = dd > nphi / 2 ? nphi - dd : dd;
     if (dd > 1 && lane == 0)
         P.shift_jump[0] = SHIFT_SEQ(P.clk);
+    if (lane == 0) { // ShiftRow::dsh: which way the previous ring's lanes lie, as k_transport_fused folded it
+        int a = my_shift % nphi, b = prev_shift % nphi;
+        a = a < 0 ? a + nphi : a, b = b < 0 ? b + nphi : b;
+        int dsh = a - b;
+        dsh = dsh > nphi / 2 ? dsh - nphi : (dsh < -(nphi / 2) ? dsh + nphi : dsh);
+        P.shift_tab[i].dsh = dsh > 0 ? 1 : (dsh < 0 ? -1 : 0);
+    }
 }
 __global__ void __launch_bounds__(256) k_ring_mean(const Dev P, int with_shift, const double *part, int nparts, int pstride)
 {
@@ -609,10 +643,11 @@ __device__ __forceinline__ void theta_star(int lim, int lsrc_l, int lsrc_r, cons
 // the cells of a lane.  geo_dt = (Rsup-Rinf) * InvSurf * dt; V the per-cell velocity (MODE 0) or vu
 // the ring velocity (MODE 1/2).  The interface mass flux F = geo_dt * v * rho* is formed once and
 // shared by all quantities: Q += q*(c) F(c) - q*(c+1) F(c+1).
-template <int C, bool ADI, bool PER, int MODE>
+// GIVEN (MODE 1 / 2): the caller brings the distance factor and geo_dt * vu (k_transport_fused: ShiftRow::d2u, gvu).
+template <int C, bool ADI, bool PER, int MODE, bool GIVEN = false>
 __device__ __forceinline__ void theta_pass(int lim, int lsrc_l, int lsrc_r, double geo_dt, double dxtheta, double invdx,
                                            double dt, const double (&V)[C], double vu, double (&S)[C], double (&Q)[4][C],
-                                           double (&E)[C])
+                                           double (&E)[C], double d2u_given = 0.0, double gvu_given = 0.0)
 {
     bool up[C];
     double d2[C], d2u = 0.0;
@@ -624,17 +659,21 @@ __device__ __forceinline__ void theta_pass(int lim, int lsrc_l, int lsrc_r, doub
             d2[c] = (up[c] ? (dxtheta - ksi) : -(dxtheta + ksi)) * invdx;
         }
     } else {
-        const double ksi = vu * dt;
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             up[c] = MODE == 1;
             d2[c] = 0.0;
         }
-        d2u = (MODE == 1 ? (dxtheta - ksi) : -(dxtheta + ksi)) * invdx;
+        if (GIVEN) {
+            d2u = d2u_given;
+        } else {
+            const double ksi = vu * dt;
+            d2u = (MODE == 1 ? (dxtheta - ksi) : -(dxtheta + ksi)) * invdx;
+        }
     }
     double rho[C], F[C + 1], rS[C];
     theta_star<C, PER, MODE>(lim, lsrc_l, lsrc_r, S, up, d2, d2u, rho);
-    const double gvu = geo_dt * vu;
+    const double gvu = GIVEN ? gvu_given : geo_dt * vu;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         F[c] = (MODE == 0 ? geo_dt * V[c] : gvu) * rho[c];

@@ -206,22 +206,20 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
         const ThetaRow t3 = crow_load(P.theta_tab, r0 - 3 >= 0 ? r0 - 3 : 0);
         convert(r0 - 3, second, t3.rmed, t3.r_omega);
     }
-    int ns_prev = 0;
+    // The per-ring scalars of an iteration are two packed rows at index m + 3 of two tables: TfRow, what no step changes
+    // (interface k, ring i and the ring m+1 that the bottom of the iteration converts; rows outside the grid hold what a
+    // clamped index would fetch), and ShiftRow of ring i, which k_ring_mean completes with every product of the ring's
+    // scalars and dt -- the loop clamps no index, forms no wave-uniform product and advances two pointers.
+    const TfRow *trow = P.tf_tab + (r0 - 3 + 3);
+    const ShiftRow *srow = (const ShiftRow *)P.shift_tab + (r0 - 3 - 2);
 
     for (int m = r0 - 3; m <= r1 + 1; ++m) {
         // ---- per-ring scalars of this iteration in one batch ----------------------------------
         const int k = m - 1, i = m - 2;
         const bool do_i = i >= r0 - 1 && i >= 0 && i < r1;
-        const RadRow rk = crow_load(P.rad_tab, (k < -1 ? -1 : k) + 1);
-        const ThetaRow ti = crow_load(P.theta_tab, do_i ? i : 0);
-        const ShiftRow si = crow_load((const ShiftRow *)P.shift_tab, do_i ? i : 0);
-        DampRow di;
-        if (DAMP)
-            di = crow_load(W.damp_tab, do_i ? i : 0);
-        // ... and of ring m+1, which the bottom of this iteration turns into specific quantities
-        typedef const double __attribute__((address_space(4))) *cdptr;
-        const cdptr tn = (cdptr)(const void *)(P.theta_tab + (m + 1 >= 0 && m + 1 < nr ? m + 1 : 0));
-        const double r_next = tn[offsetof(ThetaRow, rmed) / sizeof(double)], romega_next = tn[offsetof(ThetaRow, r_omega) / sizeof(double)];
+        const TfRow tr = crow_load(trow, 0);
+        const ShiftRow si = crow_load(srow, 0);
+        ++trow, ++srow;        const double r_next = tr.r_next, romega_next = tr.romega_next; // ring m+1
         // ---- R: slopes of ring m-1, fluxes through interface k = m-1 --------------------------
         // (the first iterations of a chunk only fill the window: the first slope that reaches a result is that of ring
         //  r0-2 -- as hs1 of the flux through interface r0-1 -- formed at m = r0-1 from the differences of rings r0-3 ..
@@ -231,13 +229,13 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
         for (int q = 0; q < NQ; ++q)
             F0[q] = 0.0;
         if (m >= r0 - (DIET ? 1 : 2)) {
-            const double idr_m = rk.idr_up;          // 1 / (Rmed[m] - Rmed[m-1]) when both rings exist
+            const double idr_m = tr.idr_up;          // 1 / (Rmed[m] - Rmed[m-1]) when both rings exist
             const bool lim_ok = k > 0 && k < nr - 1; // boundary rings carry no slope (:360-372)
             const bool open = k > 0 && k < nr;       // interface carries a flux
-            const double g = dt * rk.gphi;
+            const double g = si.g_up; // dt dphi Rinf[k]: the interface above ring i
             const double v = w[1][2]; // v_r(m-1)
             const bool up = v > 0.0;
-            const double dist = up ? (rk.dr_lo - v * dt) : -(rk.dr_hi + v * dt);
+            const double dist = up ? (tr.dr_lo - v * dt) : -(tr.dr_hi + v * dt);
             double Fc;
             double hs0[NQ]; // limited half slopes of ring m-1
 #pragma unroll
@@ -273,7 +271,7 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
         unsigned out_g = 0; // byte offset of the cell this lane stores
         double o_vr = 0.0, o_va = 0.0, o_s = 0.0, o_e = 0.0;
         if (do_i) {
-            const double invsurf = ti.invsurf;
+            const double invsurf = tr.invsurf;
             double S[1], Q[4][1], E[1], V[1]; // (theta_pass works on the cells of a lane: one here)
             const double mean = si.mean;
             const double vconst = si.vconst;
@@ -285,24 +283,22 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
                 for (int q = 0; q < 4; ++q)
                     Q[q][0] = s0 * w[2][q + 1] + (F1[q + 1] - F0[q + 1]) * invsurf;
                 E[0] = ADI ? (DIET ? s0 * w[2][NQ - 1] : er[2]) + (F1[NQ - 1] - F0[NQ - 1]) * invsurf : 0.0;
-                V[0] = vadd + ((DVP ? w[2][4] * ti.invr - ti.r_omega : vp[2]) - mean);
+                V[0] = vadd + ((DVP ? w[2][4] * tr.invr - tr.r_omega : vp[2]) - mean);
             }
-            const double dxtheta = ti.dxtheta;
-            const double invdx = ti.inv_dxtheta;
-            const double geo_dt = ti.dr_invsurf * dt;
+            const double dxtheta = tr.dxtheta;
+            const double invdx = tr.inv_dxtheta;
+            const double geo_dt = si.geo_dt;
             theta_pass<1, ADI, false, 0>(lim, 0, 0, geo_dt, dxtheta, invdx, dt, V, 0.0, S, Q, E);
-            if (P.fast_transport) {
-                if (vconst * dt > 0.0)
-                    theta_pass<1, ADI, false, 1>(lim, 0, 0, geo_dt, dxtheta, invdx, dt, V, vconst, S, Q, E);
+            if (P.fast_transport) { // (the ring's one velocity: direction, distance factor and flux factor come with the row)
+                if (si.up2)
+                    theta_pass<1, ADI, false, 1, true>(lim, 0, 0, geo_dt, dxtheta, invdx, dt, V, vconst, S, Q, E, si.d2u, si.gvu);
                 else
-                    theta_pass<1, ADI, false, 2>(lim, 0, 0, geo_dt, dxtheta, invdx, dt, V, vconst, S, Q, E);
+                    theta_pass<1, ADI, false, 2, true>(lim, 0, 0, geo_dt, dxtheta, invdx, dt, V, vconst, S, Q, E, si.d2u, si.gvu);
             }
-            int ns = si.nshift % nphi;
-            ns = ns < 0 ? ns + nphi : ns;
+            const int ns = si.ns; // Nshift[i] modulo Nphi, in [0, Nphi)
             if (i >= r0) {
-                // the previous ring sits Nshift[i] - Nshift[i-1] lanes further right
-                int dsh = ns - ns_prev;
-                dsh = dsh > nphi / 2 ? dsh - nphi : (dsh < -(nphi / 2) ? dsh + nphi : dsh);
+                // the previous ring sits Nshift[i] - Nshift[i-1] lanes further right (folded to -1, 0, 1 by k_ring_mean)
+                const int dsh = si.dsh;
                 double rp, sp;
                 if (dsh == 0) {
                     rp = rmp_prev, sp = S_prev;
@@ -313,7 +309,7 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
                 }
                 const double lpm = lane_prev(Q[2][0]); // L+ and Sigma of cell j-1
                 const double sm = lane_prev(S[0]);
-                const double invr = ti.invr, romega = ti.r_omega;
+                const double invr = tr.invr, romega = tr.r_omega;
                 const unsigned row = (unsigned)i * (unsigned)nphi;
                 int jo = jin + ns;
                 const int jout = jo >= nphi ? jo - nphi : jo;
@@ -342,22 +338,21 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
                     double sf = S[0] < P.sigma_floor_abs ? P.sigma_floor_abs : S[0];
                     double e = ADI ? clamp_energy_fast(P, E[0], sf) : 0.0;
                     if (damped) {
-                        vr = damp_select(vr, di.tvr, si.ev, vr0, 0.0);
-                        va = damp_select(va, di.tva, si.es, va0, 0.0);
-                        sf = damp_select(sf, di.tsg, si.es, s0, W.sigma_floor_abs);
+                        vr = damp_select(vr, tr.tvr, si.ev, vr0, 0.0);
+                        va = damp_select(va, tr.tva, si.es, va0, 0.0);
+                        sf = damp_select(sf, tr.tsg, si.es, s0, W.sigma_floor_abs);
                         if (ADI)
-                            e = damp_select(e, di.ten, si.es, e0, 0.0);
+                            e = damp_select(e, tr.ten, si.es, e0, 0.0);
                     }
                     o_vr = vr, o_va = va, o_s = sf, o_e = e;
                 };
-                if (DAMP && (di.tvr | di.tva | di.tsg | (ADI ? di.ten : 0)) != 0)
+                if (DAMP && (tr.tvr | tr.tva | tr.tsg | (ADI ? tr.ten : 0)) != 0)
                     new_state(true);
                 else
                     new_state(false);
                 out_g = g;
                 out_on = true;
             }
-            ns_prev = ns;
             rmp_prev = Q[0][0];
             S_prev = S[0];
         }
@@ -373,7 +368,7 @@ __device__ __forceinline__ void transport_fused_body(const Dev &P, const Dev &W,
         if (!DVP)
             vp[2] = vp[1], vp[1] = vp[0];
         if (DIET)
-            idr_prev = rk.idr_up;
+            idr_prev = tr.idr_up;
         if (m < r1 + 1) {
             convert(m + 1, nxt, r_next, romega_next);
             // The loads of fetch() must go straight into the registers convert() has just read.  Left alone, the

@@ -880,8 +880,12 @@ int fcpt_selftest_chunk_tables(int32_t nr, int32_t nphi, int32_t n_cu, int32_t a
  *                     ring_ref_damped (nr) -- 18 columns in this order
  *   FCPT_TABLE_DAMP_RANGES  9 rows of 6: row 2 q + o = (lo, hi, type, rlim, redge, tau) of field q (v_r, v_phi, Sigma, e)
  *                     at the inner (o = 0) or outer edge; row 8 = (damp_any, damp_foldable, 0, 0, 0, 0)
- *   FCPT_TABLE_AZIMUTH  nphi rows: cos(dphi j), sin(dphi j) */
-enum { FCPT_TABLE_SRC = 0, FCPT_TABLE_RAD, FCPT_TABLE_THETA, FCPT_TABLE_DAMP, FCPT_TABLE_RING, FCPT_TABLE_DAMP_RANGES, FCPT_TABLE_AZIMUTH };
+ *   FCPT_TABLE_AZIMUTH  nphi rows: cos(dphi j), sin(dphi j)
+ *   FCPT_TABLE_TF     nr + 5 rows, row m + 3 = iteration m of the fused transport kernel (TfRow, 16 columns: dr_lo, dr_hi,
+ *                     idr_up, invsurf, dxtheta, inv_dxtheta, invr, r_omega, r_next, romega_next, tvr, tva, tsg, ten, gphi,
+ *                     dr_invsurf) */
+enum { FCPT_TABLE_SRC = 0, FCPT_TABLE_RAD, FCPT_TABLE_THETA, FCPT_TABLE_DAMP, FCPT_TABLE_RING, FCPT_TABLE_DAMP_RANGES, FCPT_TABLE_AZIMUTH,
+       FCPT_TABLE_TF };
 int fcpt_selftest_ring_tables(const fcpt_desc *d, const double *radii, int32_t table, double *out, int64_t capacity,
                               int32_t *rows, int32_t *cols);
 /* Test hook: out[k] = 0.5 * flux_limiter(a[k], b[k]) (src/TransportEuler.cpp:306-337; limiter = FCPT_LIMITER_*) exactly
