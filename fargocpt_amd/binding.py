@@ -32,6 +32,8 @@ IC_PROFILE, IC_SPREADING_RING, IC_SHOCKTUBE = range(3)
 (F_SIGMA, F_VRAD, F_VAZI, F_ENERGY, F_PRESSURE, F_SOUNDSPEED, F_SCALE_HEIGHT, F_VISCOSITY,
  F_TEMPERATURE, F_POTENTIAL, F_SIGMA0, F_VRAD0, F_VAZI0, F_ENERGY0, F_QPLUS, F_QMINUS,
  F_VISC_CFAC_PHI, F_VISC_CFAC_R, F_MASSFLOW, F_ACCEL_RADIAL, F_ACCEL_AZIMUTHAL) = range(21)
+F_SG_ACCEL_RAD, F_SG_ACCEL_AZI = 21, 22   # Nr x Nphi, only while Context.selfgravity is switched on
+SG_OFF, SG_BASIC, SG_SYMMETRIC = 0, 1, 2
 VECTOR_FIELDS = (F_VRAD, F_VRAD0, F_MASSFLOW, F_ACCEL_RADIAL, F_ACCEL_AZIMUTHAL)
 TABLE_SRC, TABLE_RAD, TABLE_THETA, TABLE_DAMP, TABLE_RING, TABLE_DAMP_RANGES, TABLE_AZIMUTH = range(7)
 TABLE_TF = 7
@@ -125,6 +127,12 @@ class ParticleSlabs(C.Structure):
     """fcpt_particle_slabs: particles on one of several slabs, the records per side and call, and the running totals."""
     _fields_ = [("on", _i32), ("migrate_capacity", _i32), ("sent_inner", _u64), ("sent_outer", _u64), ("received", _u64),
                 ("deferred", _u64)]
+
+
+class SelfGravityParams(C.Structure):
+    """fcpt_selfgravity_params: the mode (SG_*), whether every kick of a step begins with the self-gravity kick, and the
+    aspect ratio and smoothing of the kernel."""
+    _fields_ = [("mode", _i32), ("in_step", _i32), ("aspect_ratio", _f64), ("thickness_smoothing_sg", _f64)]
 
 
 INTEGRATOR_MIDPOINT, INTEGRATOR_EXPLICIT = 0, 1
@@ -268,6 +276,27 @@ class Library:
         self.check(f(C.byref(d), _as_dp(radii), _i32(table), _as_dp(out), C.c_int64(out.size), C.byref(rows), C.byref(cols)),
                    "selftest_ring_tables")
         return out
+
+    def selftest_selfgravity_kernel(self, d: Desc, radii: np.ndarray, params: SelfGravityParams):
+        """(K_radial, K_azimuthal), [2 Nrad, Nphi] each: the tables Context.selfgravity would upload: host logic, no GPU."""
+        kr, kt = np.zeros((2 * d.nr_global, d.nphi)), np.zeros((2 * d.nr_global, d.nphi))
+        self.check(self.fn("selftest_selfgravity_kernel")(C.byref(d), _as_dp(radii), C.byref(params), _as_dp(kr), _as_dp(kt),
+                                                          C.c_int64(kr.size)), "selftest_selfgravity_kernel")
+        return kr, kt
+
+    def selftest_fft_radices(self, n: int):
+        """The radices of the stages of a transform of length n, in the order they run (FcptError: a refused length): no GPU."""
+        r, cnt = (_i32 * 16)(), _i32()
+        self.check(self.fn("selftest_fft_radices")(_i32(n), r, _i32(16), C.byref(cnt)), "selftest_fft_radices")
+        return [int(v) for v in r[:cnt.value]]
+
+    def selftest_fft(self, x: np.ndarray, inverse: bool = False) -> np.ndarray:
+        """The unnormalised transform of every row of x (complex128 [rows, n]) on the device."""
+        a = np.ascontiguousarray(x, dtype=np.complex128).copy()
+        assert a.ndim == 2
+        self.check(self.fn("selftest_fft")(_i32(a.shape[0]), _i32(a.shape[1]), _i32(int(bool(inverse))),
+                                           a.view(np.float64).ctypes.data_as(_dp)), "selftest_fft")
+        return a
 
     def nbody(self, G: float = 1.0) -> "NBody":
         return NBody(self, G)
@@ -637,6 +666,29 @@ class Context:
         snv = np.zeros(cap)
         self._call("particles_normals", _u64(int(step)), C.c_int64(cap), _as_dp(snv))
         return snv
+
+    # self-gravity of the gas
+    def selfgravity(self, mode: int = SG_SYMMETRIC, aspect_ratio: Optional[float] = None, thickness_smoothing_sg: float = 0.0,
+                    in_step: bool = True):
+        """Switch self-gravity on (SG_BASIC | SG_SYMMETRIC; builds the kernel spectra, blocks) or off (SG_OFF: frees).
+        aspect_ratio: h of the kernel's smoothing (default: the descriptor's AspectRatio); in_step: every kick of step /
+        step_device / run_steps begins with the self-gravity kick."""
+        h = self.desc.aspect_ratio if aspect_ratio is None else aspect_ratio
+        p = SelfGravityParams(int(mode), int(bool(in_step)), float(h), float(thickness_smoothing_sg))
+        self._call("selfgravity", C.byref(p))
+
+    def selfgravity_get(self) -> SelfGravityParams:
+        p = SelfGravityParams()
+        self._call("selfgravity_get", C.byref(p))
+        return p
+
+    def selfgravity_compute(self):
+        """Queues the evaluation of F_SG_ACCEL_RAD / F_SG_ACCEL_AZI from the current density."""
+        self._call("selfgravity_compute")
+
+    def selfgravity_kick(self, dt: float):
+        """Queues compute + update_velocities: v += dt g, in place."""
+        self._call("selfgravity_kick", _f64(dt))
 
     def allreduce_sum(self, values) -> np.ndarray:
         """SUM over the slabs of the communicator (the same bits on every slab); without one: the input."""

@@ -546,6 +546,7 @@ int fcpt_destroy(fcpt_ctx *c)
     if (c->capture_stream)
         (void)hipStreamDestroy(c->capture_stream);
     particles_free(c);
+    selfgravity_free(c);
     for (void *p : c->allocs)
         (void)hipFree(p);
     if (c->h_clk)

@@ -19,6 +19,7 @@
 
 #include "fcpt_comm.h"
 #include "fcpt_kernels.h"
+#include "fcpt_selfgravity.h"
 
 using namespace fcpt; // private header of four translation units of namespace-fcpt code around one C struct
 
@@ -59,6 +60,7 @@ struct LaunchState {
     bool has_mid;         // leapfrog: fcpt_set_bodies_midstep gave the bodies at the mid-step time
     bool join_pending;    // fcpt_step_device_begin forked the interior transport to `side`: join_side() is owed
     bool march_source;    // the option of this name after apply_options()
+    bool selfgravity;     // fcpt_selfgravity {in_step = 1}: every kick begins with the self-gravity kick
 };
 
 // the gated azimuthal launch of the fallback transport that enqueue_step left to the final boundary call of the step
@@ -155,6 +157,11 @@ struct fcpt_ctx {
     Dev graph_P;
     LaunchState graph_ls;
     ParticleLaunch graph_part = {}; // ... and the particle launch inside the cycle
+    // self-gravity of the gas (fcpt_selfgravity.hip): the parameters (mode 0: off, everything below null), the device
+    // side, and the allocations behind it -- made by fcpt_selfgravity, which drops a captured graph
+    fcpt_selfgravity_params sg_params = {0, 0, 0.0, 0.0};
+    SgDev sg = {};
+    std::vector<void *> sg_allocs;
 };
 
 
@@ -221,6 +228,10 @@ void particles_loop_launch(const fcpt_ctx *c, ParticleLaunch *L);
 void enqueue_particles_loop(fcpt_ctx *c);
 bool particles_loop_migrates(const fcpt_ctx *c);
 int enqueue_particles_migrate(fcpt_ctx *c);
+// fcpt_selfgravity.hip
+void selfgravity_free(fcpt_ctx *c);
+void enqueue_selfgravity_compute(fcpt_ctx *c, const Dev &P);
+void enqueue_selfgravity_kick(fcpt_ctx *c, const Dev &P, bool dt_from_clock, double dt); // compute + update_velocities
 // fcpt_exchange.hip
 int enqueue_exchange(fcpt_ctx *c);
 int enqueue_cfl_allreduce(fcpt_ctx *c);

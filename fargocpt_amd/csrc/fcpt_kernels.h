@@ -23,7 +23,8 @@ enum KernelId {
     KID_DISK_ON_BODY, KID_VISC_FACTORS, KID_SOURCE_MARCH_ADI, KID_SOURCE_MARCH_ADI_WIDE,
     KID_ACCEL_ON_GAS, KID_SOURCE_MARCH_ADI_ACC, KID_TRANSPORT_RADIAL_MEANS, KID_CFL_RINGS_BC,
     KID_DISK_ON_BODIES, KID_PARTICLES, KID_PARTICLES_EXPLICIT, KID_PARTICLES_EMIGRATE, KID_PARTICLES_EMIGRATE_FINISH,
-    KID_PARTICLES_IMMIGRATE, KID_PARTICLES_EMIGRATE_COUNT, KID_COUNT
+    KID_PARTICLES_IMMIGRATE, KID_PARTICLES_EMIGRATE_COUNT,
+    KID_SG_FFT_ROWS, KID_SG_TRANSPOSE, KID_SG_MULTIPLY, KID_SG_KICK, KID_COUNT
 };
 static_assert(KID_COUNT <= 64, "fcpt_profile_start selects kernels with a 64-bit mask");
 extern const char *const kKernelNames[KID_COUNT];

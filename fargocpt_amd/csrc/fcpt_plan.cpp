@@ -40,8 +40,9 @@ StepPlan plan_device_step(const Dev &P, const StepFacts &F)
     //  ideal EOS -1.2 %; at 2048 x 4096 the 1 400 workgroups folding 48 KB each cost the kernel what the launch saved)
     // (particles: their launch stands between the CFL reduction and the gas step and reads the step length, which the
     //  fold would leave only in the source kernel's prologue: the policy launch)
+    // (self-gravity: likewise -- its kick stands ahead of the source kernel and needs the final step length)
     const int want = P.opt.cfl_fold_in_source;
-    const bool fold = (want < 0 ? (long long)P.nr * P.nphi < CFL_FOLD_BELOW_CELLS : want != 0) && !F.leapfrog && F.march_source && source_march_applies(P) && cfl_by_rings(P) && !F.particles;
+    const bool fold = (want < 0 ? (long long)P.nr * P.nphi < CFL_FOLD_BELOW_CELLS : want != 0) && !F.leapfrog && F.march_source && source_march_applies(P) && cfl_by_rings(P) && !F.particles && !F.selfgravity;
     plan.cfl_policy = fold ? 2 : 1;
     // the gated launch of the fallback transport together with the final boundary call, where that call will be
     // nothing but the ghost-ring kernel and does not ride in the next CFL launch (grids below 4 M cells)

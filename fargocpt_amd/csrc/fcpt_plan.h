@@ -31,6 +31,7 @@ struct StepFacts {
     bool damping_configured, slab_damped;
     bool march_source;               // LaunchState's: the option after apply_options()
     bool particles;                  // fcpt_particles_follow_run_steps with particles: their launch stands behind the CFL launch
+    bool selfgravity = false;        // fcpt_selfgravity {in_step = 1}: the kick begins with launches that read the step length
 };
 
 // One iteration of the device-resident loop (fcpt_run_steps without neighbours).  The first three are plan_device_step()'s;

@@ -63,6 +63,7 @@ StepFacts step_facts(const fcpt_ctx *c)
     F.slab_damped = c->damp_any;
     F.march_source = c->ls.march_source;
     F.particles = c->part_follow && c->part.n > 0;
+    F.selfgravity = c->ls.selfgravity;
     return F;
 }
 
@@ -90,6 +91,10 @@ KickResult enqueue_kick(fcpt_ctx *c, const Dev &P, bool fold_bc, const StepPlan 
     hipStream_t st = c->stream;
     KickResult r = {false, 0, false};
     const bool fold_pending = plan.cfl_policy == 2;
+    // update_with_sourceterms begins with selfgravity::compute(data, dt, true) (SourceEuler.cpp:435-441): v += dt g in place,
+    // launches of their own ahead of everything else (plan_device_step leaves no CFL fold pending with self-gravity)
+    if (c->ls.selfgravity)
+        enqueue_selfgravity_kick(c, P, true, 0.0);
     // one pass: (v[, e]) -> (v_b[, e_b])
     const bool fold_cfl = fold_pending && c->ls.march_source && source_march_applies(P);
     if (fold_pending && !fold_cfl)

@@ -5,11 +5,13 @@
 // for the default unit system (l0 = 1 au, m0 = 1 solMass).  A key the reference's reader does not know is
 // fatal, as in the reference (src/config.cpp:134-138: a typo must not silently change the physics); --lenient
 // downgrades that to a warning.  Keys the reference knows but the gas path does not consume are accepted (listed
-// unless -q); features outside the path that a setup switches on (self-gravity, FLD ...) are refused.
+// unless -q); features outside the path that a setup switches on (FLD, self-gravity with the Bessel kernel ...) are
+// refused.  SelfGravity runs with SelfGravityMode: basic | symmetric (read_selfgravity_setup).
 #include "driver.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <fstream>
 #include <sstream>
 
@@ -434,6 +436,10 @@ void check_keys(const Config &c, bool lenient, bool master)
         exit(1);
     for (const char *k : kRefusedWhenOn)
         if (c.has(k) && c.flag(k, false)) {
+            // SelfGravity with SelfGravityMode written out is read_selfgravity_setup's: it runs basic and symmetric and
+            // refuses the rest by name.  Without the key the reference's default is the Bessel kernel: refused here
+            if (!strcmp(k, "selfgravity") && c.has("SelfGravityMode"))
+                continue;
             fprintf(stderr, "fargocpt_hip: '%s' is switched on, but that part of the reference is outside this driver's "
                             "gas path\n", k);
             exit(2);
@@ -501,6 +507,58 @@ ParticleSetup read_particle_setup(const Config &c, const Units &u, const fcpt_de
     ps.escape_min = std::max(num(c, u, "ParticleMinimumEscapeRadius", d.rmin, K_LEN), d.rmin); // clamped to the grid (:943-955)
     ps.escape_max = std::min(num(c, u, "ParticleMaximumEscapeRadius", d.rmax, K_LEN), d.rmax);
     return ps;
+}
+
+[[noreturn]] static void refuse_selfgravity(const char *what)
+{
+    fprintf(stderr, "fargocpt_hip: %s is not supported with SelfGravity\n", what);
+    exit(2);
+}
+
+// SelfGravity: yes with SelfGravityMode: basic | symmetric (parameters.cpp:698-728); what the library's solver does not
+// cover is refused here, each with the key that asks for it, before any device is asked for
+SelfGravitySetup read_selfgravity_setup(const Config &c, const Units &u, const fcpt_desc &d, bool several_ranks)
+{
+    SelfGravitySetup sg;
+    if (!(c.has("SelfGravity") && c.flag("SelfGravity", false)))
+        return sg;
+    sg.on = true;
+    const std::string mode = lower(c.str("SelfGravityMode", "besselkernel"));
+    if (mode == "basic")
+        sg.mode = FCPT_SG_BASIC;
+    else if (mode == "symmetric")
+        sg.mode = FCPT_SG_SYMMETRIC;
+    else if (mode == "besselkernel")
+        refuse_selfgravity("SelfGravityMode: besselkernel (it rescales the scale height by Toomre's Q inside the source step; "
+                           "basic and symmetric run)");
+    else {
+        fprintf(stderr, "fargocpt_hip: SelfGravityMode: %s is not supported. Choices: basic, symmetric\n", mode.c_str());
+        exit(2);
+    }
+    if (d.eos == FCPT_EOS_IDEAL)
+        refuse_selfgravity("EquationOfState: ideal (the kernel's refresh from the mass-averaged aspect ratio is not built)");
+    if (d.radial_spacing != FCPT_SPACING_LOGARITHMIC)
+        refuse_selfgravity("RadialSpacing other than Logarithmic (the polar method needs a logarithmic grid)");
+    if (several_ranks)
+        refuse_selfgravity("--ranks > 1 (the solver needs the whole grid in one slab)");
+    const int lengths[2] = {d.nphi, 2 * d.nr_global};
+    const char *keys[2] = {"Naz", "2 x Nrad"};
+    for (int k = 0; k < 2; ++k) {
+        int32_t count = 0;
+        if (fcpt_selftest_fft_radices(lengths[k], nullptr, 0, &count) != FCPT_OK) {
+            fprintf(stderr, "fargocpt_hip: %s = %d is not supported with SelfGravity: a transform length must be at most %d "
+                            "and have no prime factor above 5\n", keys[k], lengths[k], FCPT_FFT_MAX_N);
+            exit(2);
+        }
+    }
+    sg.aspect_ratio = d.aspect_ratio;
+    sg.thickness_smoothing_sg = num(c, u, "ThicknessSmoothingSG", 1.2);
+    sg.write_rad = c.flag("WriteSGAccelRad", false);
+    sg.write_azi = c.flag("WriteSGAccelAzi", false);
+    // IndirectTermDiskOnDisk: auto = yes with self-gravity (parameters.cpp:809-817)
+    const std::string it = lower(c.str("IndirectTermDiskOnDisk", "auto"));
+    sg.indirect_disk = it == "auto" || c.flag("IndirectTermDiskOnDisk", true);
+    return sg;
 }
 
 // the nbody list: star + planets; a setup without one has the hydro centre alone

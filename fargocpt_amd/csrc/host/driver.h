@@ -70,6 +70,17 @@ struct ParticleSetup {
 // the Particle* keys, and the refusals (exit 2) of what the library's particle step does not cover
 ParticleSetup read_particle_setup(const Config &c, const Units &u, const fcpt_desc &d, bool have_dust_seed, bool several_ranks);
 
+// Self-gravity of the gas: SelfGravity with SelfGravityMode: basic | symmetric (parameters.cpp:698-728)
+struct SelfGravitySetup {
+    bool on = false;
+    int mode = FCPT_SG_OFF;
+    double aspect_ratio = 0, thickness_smoothing_sg = 0;
+    bool write_rad = false, write_azi = false; // WriteSGAccelRad / WriteSGAccelAzi
+    bool indirect_disk = false;                // IndirectTermDiskOnDisk (auto: yes with self-gravity)
+};
+// the keys, and the refusals (exit 2) of what the library's solver does not cover
+SelfGravitySetup read_selfgravity_setup(const Config &c, const Units &u, const fcpt_desc &d, bool several_ranks);
+
 struct Body {
     double a, m, phase, rsm_factor;
     double rampup; // "ramp-up time" in orbital periods (planet.cpp:166-179)
@@ -105,6 +116,7 @@ struct Driver {
     std::vector<double> radii; // interface radii of the global grid (fcpt_radii)
     std::string outdir, cfgpath;
     bool quiet = false;
+    SelfGravitySetup sg;
 };
 
 void mkdirs(const std::string &p);

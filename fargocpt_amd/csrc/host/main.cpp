@@ -349,6 +349,50 @@ void connect_ranks(const Driver &dr, const std::string &transport, int ndev)
                transport == "host" ? "host-staged" : "RCCL", ndev);
 }
 
+// selfgravity::init (selfgravity.cpp:219-301): the kernel spectra and one compute(data, 0, false); every kick of the
+// library's step then begins with the self-gravity kick.  A fresh run also takes the initial v_phi of a self-gravitating
+// disk (init.cpp:1720-1746 with selfgravity::init_azimuthal_velocity, selfgravity.cpp:749-781): in rows 0 .. Nr-2
+//   v_phi = Rmed sqrt(omega_cell^2 - <g_r> / Rmed) - OmegaFrame Rmed,   omega_cell = v_phi0 / Rmed,
+// with <g_r> the ring mean and v_phi0 the speed without self-gravity, which fcpt_initial_fields has left (minus the
+// frame's) in the grid; the last row stays at the frame's speed alone until the boundary call.  A restart stores nothing
+// extra: the velocities come from the snapshot, the accelerations are recomputed by the first kick.
+void init_selfgravity(Driver &dr, bool restarting)
+{
+    const fcpt_desc &d = dr.desc;
+    const fcpt_selfgravity_params p = {dr.sg.mode, 1, dr.sg.aspect_ratio, dr.sg.thickness_smoothing_sg};
+    CHECK(fcpt_selfgravity(dr.ctx, &p));
+    CHECK(fcpt_selfgravity_compute(dr.ctx));
+    if (restarting)
+        return;
+    const int nr = d.nr_global, nphi = d.nphi;
+    std::vector<double> g_r((size_t)nr * nphi), vazi((size_t)nr * nphi);
+    CHECK(fcpt_download(dr.ctx, FCPT_F_SG_ACCEL_RAD, g_r.data()));
+    CHECK(fcpt_download(dr.ctx, FCPT_F_VAZI, vazi.data()));
+    for (int i = 0; i < nr; ++i) {
+        const double ri = dr.radii[i], rs = dr.radii[i + 1];
+        double rmed = 2.0 / 3.0 * (rs * rs * rs - ri * ri * ri);
+        rmed = rmed / (rs * rs - ri * ri);
+        double mean = 0.0; // mpi_make1Dprofile: the plain sum over the ring, divided by Nphi
+        for (int j = 0; j < nphi; ++j)
+            mean += g_r[(size_t)i * nphi + j];
+        mean /= (double)nphi;
+        for (int j = 0; j < nphi; ++j) {
+            double &v = vazi[(size_t)i * nphi + j];
+            if (i == nr - 1) {
+                v = -d.omega_frame * rmed;
+                continue;
+            }
+            const double omega_cell = (v + d.omega_frame * rmed) / rmed;
+            const double temp = omega_cell * omega_cell - mean / rmed;
+            if (temp < 0 && j == 0)
+                fprintf(stderr, "fargocpt_hip: Radicand %g < 0 in init_azimuthal_velocity! Maybe ThicknessSmoothingSG (%g) is too small!\n",
+                        temp, dr.sg.thickness_smoothing_sg);
+            v = rmed * std::sqrt(temp) - d.omega_frame * rmed;
+        }
+    }
+    CHECK(fcpt_upload(dr.ctx, FCPT_F_VAZI, vazi.data()));
+}
+
 // irradiating bodies: 'temperature', 'radius', 'irradiation ramp-up time' (planetary_system.cpp:160-250)
 void set_irradiation(const Driver &dr, const Config &cfg)
 {
@@ -387,9 +431,13 @@ int main(int argc, char **argv)
     check_keys(cfg, opt.lenient, dr.slab.master());
     Particles pt{&dr};
     pt.ps = read_particle_setup(cfg, dr.units, dr.desc, opt.have_dust_seed, opt.want_ranks > 1 || dr.slab.nranks > 1);
+    dr.sg = read_selfgravity_setup(cfg, dr.units, dr.desc, opt.want_ranks > 1 || dr.slab.nranks > 1);
     BodySystem bs{&dr};
     bs.free = opt.bodies_mode == "free";
     check_bodies_mode(cfg, dr, bs);
+    if (dr.sg.on && dr.sg.indirect_disk && !(bs.free && bs.disk_feedback) && !dr.quiet)
+        fprintf(stderr, "fargocpt_hip: note: IndirectTermDiskOnDisk (auto: yes with SelfGravity) is not applied: the disk's pull "
+                        "on the star reaches the frame only with --bodies free and DiskFeedback: yes\n");
     // The parent of --ranks forks and execs here, unchanged: before the first library call that can open a device
     // (fcpt_device_count in create_on_device), so it has never touched a GPU.  The n ranks run, it only waits for them.
     if (opt.want_ranks > 1 && !ranked)
@@ -405,6 +453,8 @@ int main(int argc, char **argv)
     bs.init(cfg);
     bs.set(0.0);
     set_irradiation(dr, cfg);
+    if (dr.sg.on)
+        init_selfgravity(dr, restarting);
     CHECK(fcpt_init_physics(dr.ctx));
     pt.init();
     if (pt.ps.on && !restarting)

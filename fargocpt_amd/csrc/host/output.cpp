@@ -189,11 +189,15 @@ void write_static_files(const Driver &dr)
                        {"vrad", "cm s^-1", vel, true},
                        {"vazi", "cm s^-1", vel, false},
                        {"energy", "erg cm^-2", mass / (tim * tim), false},
-                       {"Temperature", "K", temp, false}};
+                       {"Temperature", "K", temp, false},
+                       {"a_sg_rad", "cm s^-2", len / (tim * tim), false},
+                       {"a_sg_azi", "cm s^-2", len / (tim * tim), false}};
     f = open_or_die(dr.outdir + "info2D.yml", "w");
     fprintf(f, "# 2D output variable descriptions\n# version 0.1\n\n");
     for (const G &g : grids) {
         if ((!strcmp(g.name, "energy") || !strcmp(g.name, "Temperature")) && d.eos != FCPT_EOS_IDEAL)
+            continue;
+        if ((!strcmp(g.name, "a_sg_rad") && !(dr.sg.on && dr.sg.write_rad)) || (!strcmp(g.name, "a_sg_azi") && !(dr.sg.on && dr.sg.write_azi)))
             continue;
         fprintf(f, "%s:\n  cgs symbols: %s\n  code_to_cgs_factor: %.17g\n  unit: %.17g %s\n  Nrad: %d\n  Nazi: %d\n",
                 g.name, g.sym, g.v, g.v, g.sym, g.vec ? d.nr_global + 1 : d.nr_global, d.nphi);
@@ -210,8 +214,9 @@ struct SnapshotGrid {
     const char *file;
     int restart;
 };
-static std::vector<SnapshotGrid> snapshot_grids(const fcpt_desc &d)
+static std::vector<SnapshotGrid> snapshot_grids(const Driver &dr)
 {
+    const fcpt_desc &d = dr.desc;
     std::vector<SnapshotGrid> grids = {{FCPT_F_SIGMA, FCPT_F_SIGMA0, "Sigma.dat", 2},
                                        {FCPT_F_VRAD, FCPT_F_VRAD0, "vrad.dat", 2},
                                        {FCPT_F_VAZI, FCPT_F_VAZI0, "vazi.dat", 2}};
@@ -222,6 +227,11 @@ static std::vector<SnapshotGrid> snapshot_grids(const fcpt_desc &d)
         grids.push_back({FCPT_F_QPLUS, -1, "Qplus.dat", 1});
         grids.push_back({FCPT_F_QMINUS, -1, "Qminus.dat", 1});
     }
+    // WriteSGAccelRad / WriteSGAccelAzi (data.cpp:61-68): what the last kick's compute left; a restart recomputes them
+    if (dr.sg.on && dr.sg.write_rad)
+        grids.push_back({FCPT_F_SG_ACCEL_RAD, -1, "a_sg_rad.dat", 0});
+    if (dr.sg.on && dr.sg.write_azi)
+        grids.push_back({FCPT_F_SG_ACCEL_AZI, -1, "a_sg_azi.dat", 0});
     return grids;
 }
 
@@ -257,7 +267,7 @@ void write_snapshot(const Driver &dr, const BodySystem &bs, Particles &pt, unsig
     fcpt_clock clk;
     CHECK(fcpt_get_clock(dr.ctx, &clk));
     const std::string dir = dr.outdir + "snapshots/" + (name ? std::string(name) : std::to_string(nsnap)) + "/";
-    const std::vector<SnapshotGrid> grids = snapshot_grids(d);
+    const std::vector<SnapshotGrid> grids = snapshot_grids(dr);
     const bool massflow = d.write_massflow && !name;
     // MPI_File_open(MPI_MODE_CREATE) is collective in the reference; here rank 0 creates the directory and the
     // empty files, then every slab writes its window into them
@@ -318,7 +328,7 @@ misc_entry restart_load(const Driver &dr, BodySystem &bs, Particles &pt, const s
     if (fread(&misc, sizeof(misc), 1, mf) != 1)
         die_cannot("read", restart_dir + "misc.bin");
     fclose(mf);
-    const std::vector<SnapshotGrid> grids = snapshot_grids(dr.desc);
+    const std::vector<SnapshotGrid> grids = snapshot_grids(dr);
     if (needs_reference(dr.desc))
         for (const SnapshotGrid &g : grids)
             if (g.field0 >= 0)

@@ -12,7 +12,8 @@ const char *const kKernelNames[KID_COUNT] = {
     "k_exchange_copy", "k_disk_on_body", "k_visc_factors", "k_source_march_adi", "k_source_march_adi_wide",
     "k_accel_on_gas", "k_source_march_adi_acc",
     "k_transport_radial_means", "k_cfl_rings_bc", "k_disk_on_bodies", "k_particles_step", "k_particles_step_explicit",
-    "k_particles_emigrate", "k_particles_emigrate_finish", "k_particles_immigrate", "k_particles_emigrate_count"};
+    "k_particles_emigrate", "k_particles_emigrate_finish", "k_particles_immigrate", "k_particles_emigrate_count",
+    "k_sg_fft_rows", "k_sg_transpose", "k_sg_multiply", "k_sg_kick"};
 
 thread_local Profiler *g_prof = nullptr;
 

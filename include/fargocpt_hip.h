@@ -101,7 +101,12 @@ enum {
      * (src/Pframeforce.cpp:96-189) left for the last source step (rows 0 and Nr are never written: zero) */
     FCPT_F_ACCEL_RADIAL = 19,
     FCPT_F_ACCEL_AZIMUTHAL = 20,
-    FCPT_F_COUNT = 21
+    /* SG_ACCEL_RAD / SG_ACCEL_AZI (src/data.cpp:61-68), Nr x Nphi, cell-centred: the acceleration of the gas by its own
+     * gravity as the last fcpt_selfgravity_compute / _kick (or in-step kick) left it; only while fcpt_selfgravity is
+     * switched on, FCPT_EINVAL otherwise */
+    FCPT_F_SG_ACCEL_RAD = 21,
+    FCPT_F_SG_ACCEL_AZI = 22,
+    FCPT_F_COUNT = 23
 };
 
 /*
@@ -705,6 +710,59 @@ int fcpt_particles_migrate(fcpt_ctx *ctx);
 /* The generator itself, on the host (no GPU needed): ten rounds of Philox4x32, and the deviate above. */
 void fcpt_philox4x32(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 double fcpt_particles_std_normal(uint64_t seed, uint64_t id, uint64_t step);
+
+/* ---- self-gravity of the gas ------------------------------------------------------------------------------------------
+ * selfgravity::compute (src/selfgravity.cpp:303-319) in the modes SelfGravityMode: basic (sg_B) and symmetric (sg_S): the
+ * polar convolution of Baruteau (2008) on a logarithmic grid.  The reduced densities S_r = Sigma sqrt(Rmed / Rmed[0]) and
+ * S_t = S_r Rmed / Rmed[0] are laid into the lower Nr rows of a zero-padded array of 2 Nr rows (:321-416), transformed,
+ * multiplied with the spectra of the kernel tables K_radial / K_azimuthal (:418-518, built on the host with libm from Radii[]
+ * and epsilon = thickness_smoothing_sg * aspect_ratio, or lambda_sq and chi_sq of :171-179) and with -G, transformed back
+ * and weighted ring by ring with r_step t_step / (2 Nr Nphi) and the powers of Rmed / Rmed[0] (:520-703).  The results are
+ * the grids FCPT_F_SG_ACCEL_RAD / _AZI.  The kick is update_velocities (:712-747): v_r rows 1 .. Nr-1 from g_r of rows i and
+ * i-1, v_phi rows 0 .. Nr-1 from g_phi of columns j and j-1 (wrapping); v_r rows 0 and Nr stay untouched.
+ *
+ * The transforms are the library's own (csrc/kernels/fft.h: a mixed-radix Stockham transform in LDS, radices 2, 3, 4, 5, one
+ * row per workgroup); no FFT library is linked.  Both real fields ride in one complex transform and are separated by
+ * Hermitian symmetry in the multiply.
+ * Departures from the reference: (1) FFTW takes any length; here Nphi and 2 Nr must each be at most 8192 and have no
+ * prime factor above 5, anything else is refused with FCPT_EINVAL and the length named.  (2) One slab only: a context that is
+ * one of several slabs is refused.  (3) SelfGravityMode: besselkernel, which rescales the scale height by Toomre's Q
+ * inside the source step, is not built.  (4) The caller supplies the aspect ratio h of the kernel; the reference's refresh
+ * from the mass-averaged aspect ratio every 20 steps under the ideal EOS (:186-214) is the caller's: call fcpt_selfgravity
+ * again.  The result agrees with the reference's to rounding, not to the bit (another transform, another order of sums).
+ *
+ * Memory: 96 bytes per cell for the transforms and spectra plus the two grids, allocated by fcpt_selfgravity and freed by
+ * mode 0 or fcpt_destroy; a context that never calls fcpt_selfgravity allocates, launches and computes what it did before.
+ * in_step = 1: every gas kick of fcpt_step / fcpt_step_device / fcpt_run_steps begins with compute + kick over the kick's own
+ * step length (update_with_sourceterms, src/SourceEuler.cpp:435-441; Leapfrog: both half kicks with dt / 2,
+ * src/simulation.cpp:324, 379), read from the device clock: no host round trip, serial launches on the context's stream, also
+ * inside the captured graph of fcpt_run_steps.  The step length must be final before the kick, so with in_step the CFL fold
+ * inside the marching source kernel gives way to the policy launch (the gas bits are the same).
+ * fcpt_selfgravity returns FCPT_EINVAL, fcpt_last_error naming the reason, for: a grid that is not logarithmic
+ * (selfgravity.cpp:222), a context that is one of several slabs, a refused length, aspect_ratio <= 0, an unknown mode.  A
+ * refused call changes nothing.  Blocks (it builds, uploads and transforms the kernel tables). */
+#define FCPT_FFT_MAX_N 8192 /* the longest transform: Nphi and 2 Nr of a self-gravitating grid */
+enum { FCPT_SG_OFF = 0, FCPT_SG_BASIC = 1, FCPT_SG_SYMMETRIC = 2 };
+typedef struct fcpt_selfgravity_params {
+    int32_t mode;     /* 0 off, FCPT_SG_BASIC 1, FCPT_SG_SYMMETRIC 2 */
+    int32_t in_step;  /* 1: every kick of fcpt_step / _step_device / _run_steps begins with the SG kick */
+    double aspect_ratio, thickness_smoothing_sg;
+} fcpt_selfgravity_params;
+int fcpt_selfgravity(fcpt_ctx *ctx, const fcpt_selfgravity_params *p); /* (re)builds the kernel spectra; mode 0 frees */
+int fcpt_selfgravity_get(fcpt_ctx *ctx, fcpt_selfgravity_params *out);
+/* compute(data, 0, false): fills the two grids from the current density; asynchronous, no host wait */
+int fcpt_selfgravity_compute(fcpt_ctx *ctx);
+/* compute(data, dt, true): compute + update_velocities; asynchronous */
+int fcpt_selfgravity_kick(fcpt_ctx *ctx, double dt);
+/* Test hooks.  _kernel (no GPU needed): the tables K_radial and K_azimuthal fcpt_selfgravity would upload for this descriptor,
+ * these global radii and parameters, 2 Nrad x Nphi doubles each, row-major (capacity: doubles per array).  _fft_radices (no
+ * GPU needed): the radices of the stages of a transform of length n, in the order they run; FCPT_EINVAL for a refused length.
+ * _fft: `rows` rows of n interleaved complex numbers (re, im) transformed in place on the device with exp(-2 pi i jk / n)
+ * (inverse != 0: exp(+2 pi i jk / n)), unnormalised; blocks. */
+int fcpt_selftest_selfgravity_kernel(const fcpt_desc *d, const double *radii, const fcpt_selfgravity_params *p,
+                                     double *k_radial, double *k_azimuthal, int64_t capacity);
+int fcpt_selftest_fft_radices(int32_t n, int32_t *radices, int32_t capacity, int32_t *count);
+int fcpt_selftest_fft(int32_t rows, int32_t n, int32_t inverse, double *interleaved);
 
 /* ---- the hot path -------------------------------------------------------- */
 
